@@ -2,10 +2,25 @@
 """Headline benchmark: distributed El::Gemm TFLOP/s on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+                  [--dump-outputs DIR] [--full]
   (N > 1: one process per GPU.  Under torch.distributed.run RANK / LOCAL_RANK /
    WORLD_SIZE / MASTER_* come from the environment; with WORLD_SIZE unset this
    script starts the N rank processes itself with that same environment
    (launch_ranks) and exits with the first failing rank's status)
+
+A plain run does only what the headline figure needs: it sets the operands up,
+runs W warm-up steps, times K steps, writes the outputs when --dump-outputs is
+given and prints the line.  Everything else described below (the full-size
+associativity check of the timed point, the N > 1 residual, the C3 / C4 / C5 /
+C1 points on one GPU, the entrywise and [MC,MR]-input figures of --config c5 /
+c4, the CPU baseline) runs only with --full, and then as it always did.
+
+--dump-outputs DIR writes, after the timed steps, the C the last timed step
+left (what a caller of El::Gemm receives) to DIR/C.npy, gathered on rank 0:
+the whole matrix when it fits in 32 MiB as float64 (float32 for the narrower
+types), otherwise a fixed, seeded sample of 256 x 256 tiles (shape
+(tiles, 256, 256), the two corner tiles among them).  Inputs come from the
+counter hash, so the same arguments give the same inputs in every run.
 
 One step = one El::Gemm(...) on DistMatrix operands already resident in HBM,
 inputs from the grid-independent counter hash (synthetic data, Uniform(-0.1,
@@ -214,6 +229,52 @@ def verify_point(el, grid, DT, dtype: str, oA, step, A, B, C, k: int, alpha: flo
     return {"check": f"associativity ||Y - C_f X||_F/||Y||_F, {nrhs} rhs, at this point's full size "
                      "(tests/blas_like/Gemm.cpp:15-49)",
             "residual": r, "tol": tol, "tol_rule": rule, "ok": bool(r <= tol)}
+
+
+DUMP_WHOLE_BYTES = 32 << 20   # a C of at most this size is written whole
+DUMP_TILE, DUMP_TILES = 256, 64  # otherwise 64 tiles of 256 x 256 (32 MiB as float64)
+
+
+def dump_tiles(m: int, n: int) -> list[tuple[int, int]]:
+    """Top-left corners of the sampled tiles of an m x n output: the two corner
+    tiles, then seeded positions anywhere (not tile-aligned).  A function of
+    the shape alone, so every rank and every run picks the same ones."""
+    import numpy as np
+    t = DUMP_TILE
+    rng = np.random.default_rng(0xE1E3)
+    out = [(0, 0), (m - t, n - t)]
+    while len(out) < DUMP_TILES:
+        out.append((int(rng.integers(0, m - t + 1)), int(rng.integers(0, n - t + 1))))
+    return out
+
+
+def dump_outputs(el, grid, DT, C, directory: str) -> None:
+    """--dump-outputs: C as the last timed step left it, to directory/C.npy
+    (float64 for f64, float32 for f32 / f16 / bf16).  Collective: each piece is
+    gathered to rank 0 through a [CIRC,CIRC] copy, and rank 0 writes."""
+    import numpy as np
+    m, n = C.Height(), C.Width()
+    wide = np.float64 if DT == el.F64 else np.float32
+
+    def gather(M):
+        R = el.DistMatrix(grid, DT, el.CIRC, el.CIRC, C.device)
+        R.assign(M)
+        a = R.get_local()
+        if grid.vc_rank != 0:
+            return None
+        if DT == el.BF16:  # travels as uint16 bit patterns: the high half of a float32
+            return (a.astype(np.uint32) << 16).view(np.float32)
+        return a.astype(wide, copy=False)
+
+    if m * n * np.dtype(wide).itemsize <= DUMP_WHOLE_BYTES or min(m, n) < DUMP_TILE:
+        arr = gather(C)
+    else:
+        t = DUMP_TILE
+        parts = [gather(C((i, i + t), (j, j + t))) for i, j in dump_tiles(m, n)]
+        arr = None if grid.vc_rank != 0 else np.stack(parts)
+    if grid.vc_rank == 0:
+        os.makedirs(directory, exist_ok=True)
+        np.save(os.path.join(directory, "C.npy"), np.ascontiguousarray(arr))
 
 
 def est_seconds(flops: float, dtype: str, world: int) -> float:
@@ -452,6 +513,13 @@ def main():
     ap.add_argument("--dtype", choices=["f64", "f32", "bf16", "f16"], default=None)
     ap.add_argument("--nb", type=int, default=128, help="El::Blocksize (communication panel)")
     ap.add_argument("--kc", type=int, default=0, help="compute panel (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the full-size check of the timed "
+                         "point, the N>1 residual, the other configurations and the CPU baseline "
+                         "(the --no-* / --extra-configs / --c3-steps options below select among those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the C of the last timed step to DIR/C.npy "
+                         "(whole, or a fixed seeded sample of tiles when larger than 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-residual", action="store_true", help="skip the N>1 associativity check")
     ap.add_argument("--c3-steps", type=int, default=2, help="timed steps of the N=1 C3 point")
@@ -544,7 +612,7 @@ def main():
 
     step_flops = 2.0 * m * n * k
     residual = None
-    if world > 1 and not args.no_residual:
+    if args.full and world > 1 and not args.no_residual:
         # correctness on this very grid before timing (no oracle): the reference's
         # associativity check through the distributed path
         stage("residual", 300)
@@ -570,6 +638,10 @@ def main():
     elapsed = time.perf_counter() - t0
     prof = profile_summary(L, ctypes)
     L.call("elx_set_profiling", 0)
+    if args.dump_outputs:
+        stage("dump", 300)
+        dump_outputs(el, grid, DT, C, args.dump_outputs)
+        barrier()
 
     def max_over_ranks(x: float) -> float:
         if dist is None:
@@ -632,14 +704,15 @@ def main():
     L.call("elx_reserved_cus", ctypes.byref(cus))
     out["config"]["comm_reserved_cus"] = cus.value
 
-    # the timed point itself, checked at full size through the same path (one
-    # more, untimed step)
-    stage("verify", 120 + 4 * est_seconds(step_flops, dtype, world))
-    try:
-        out["verify"] = verify_point(el, grid, DT, dtype, oA, step, A, B, C, k)
-    except Exception as e:
-        out["verify"] = {"error": str(e), "ok": False}
-    barrier()
+    # --full: the timed point itself, checked at full size through the same path
+    # (one more, untimed step)
+    if args.full:
+        stage("verify", 120 + 4 * est_seconds(step_flops, dtype, world))
+        try:
+            out["verify"] = verify_point(el, grid, DT, dtype, oA, step, A, B, C, k)
+        except Exception as e:
+            out["verify"] = {"error": str(e), "ok": False}
+        barrier()
 
     # from here on the line exists: if a later (optional) stage overruns, the
     # watchdog prints it with that stage marked and the process still exits
@@ -662,7 +735,8 @@ def main():
             out[key] = {"error": str(e)}
         epitaph(None)
 
-    if config == "c5":
+    # everything from here to the report runs with --full only
+    if args.full and config == "c5":
         # DistMatrix Axpy / Hadamard on the [MC,MR] operands (no exchange: each
         # rank updates its local block); HBM bytes 3 x local elements x size
         def entrywise():
@@ -684,7 +758,7 @@ def main():
                             "frac_of_hbm": round(gbs / HBM_PEAK_GBS, 4)}
             return ew
         extra("entrywise", entrywise)
-    if config == "c4":
+    if args.full and config == "c4":
         # the same product with [MC,MR] inputs: SUMMA_DOT's read
         # proxies first redistribute A and B to [VC,*] (TN.hpp:384-391), inside
         # the timed region
@@ -705,14 +779,14 @@ def main():
                     "value": round(2.0 * m * n * k * args.steps / dt / 1e12, 3), "unit": "TFLOP/s",
                     "ms_per_step": round(dt / args.steps * 1e3, 3)}
         extra("c4_mcmr_inputs", mcmr)
-    if world == 1 and config == "c2" and not args.n and not args.no_c3_1gpu:
+    if args.full and world == 1 and config == "c2" and not args.n and not args.no_c3_1gpu:
         # the same problem as the driver's N>1 lines (C3, n = 65536, kc = 8192
         # compute panels as EffectivePanel picks on grids > 1x1), on this one GPU
         A = B = C = None  # release the C2 operands before the n = 65536 ones
         extra("c3_1gpu", lambda: c3_one_gpu(el, L, grid, barrier, args.c3_steps, 1, args.kc))
         # C3 is "fp64/fp32": the fp32 half of the same problem
         extra("c3_1gpu_f32", lambda: c3_one_gpu(el, L, grid, barrier, args.c3_steps, 1, args.kc, dtype="f32"))
-    extras = (world == 1 and not args.no_extra_configs) or (world > 1 and args.extra_configs)
+    extras = args.full and ((world == 1 and not args.no_extra_configs) or (world > 1 and args.extra_configs))
     if config in ("c2", "c3") and (not args.n or rehearse) and extras:
         # the other BASELINE configs, measured in the same run on the same grid
         # (N = 1: c4_1gpu / c5_1gpu; N > 1 with --extra-configs: c4 / c5 on
@@ -723,7 +797,7 @@ def main():
             key = (f"{cfg}_1gpu" if world == 1 else cfg) + ("_f16" if half == "f16" else "")
             extra(key, lambda cfg=cfg, st=st, half=half: config_point(el, L, grid, barrier, max_over_ranks, cfg, st, 1,
                                                                       world, args.n, half))
-    if world == 1 and config == "c2" and not args.n and not args.no_extra_configs:
+    if args.full and world == 1 and config == "c2" and not args.n and not args.no_extra_configs:
         # C1's problem (NN f64 4096^3) on the GPU, beside the CPU leg's same problem
         def c1():
             stage("c1_1gpu", 120)
@@ -743,7 +817,7 @@ def main():
                     "value": round(2.0 * n1 ** 3 / dt / 1e12, 3), "unit": "TFLOP/s", "steps": 20,
                     "ms_per_step": round(dt * 1e3, 3)}
         extra("c1_1gpu", c1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def cpu():
             stage("cpu_baseline", 300)
             return cpu_baseline()

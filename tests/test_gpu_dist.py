@@ -334,7 +334,7 @@ def test_gpu_initialize_rccl_world_from_launcher_env():
 
 @pytest.mark.parametrize("hang,line", [("timed", False), ("cpu_baseline", True)])
 def test_gpu_bench_stage_hang(hang, line):
-    """bench.py under an injected hang (ELX_BENCH_HANG): the watchdog ends the
+    """bench.py --full under an injected hang (ELX_BENCH_HANG): the watchdog ends the
     run with ELX_WATCHDOG_EXIT naming the stage.  In the timed stage no line is
     printed; in a stage after the main point the line is still printed, with
     that stage marked and an "incomplete" field, and the exit status is STILL
@@ -345,7 +345,7 @@ def test_gpu_bench_stage_hang(hang, line):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "2048", "--steps", "1",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=200,
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=200,
                        env=dict(os.environ, ELX_BENCH_HANG=hang))
     assert p.returncode == el.WATCHDOG_EXIT, p.stdout + p.stderr
     assert f"FATAL in stage '{hang}'" in p.stderr
@@ -359,7 +359,7 @@ def test_gpu_bench_stage_hang(hang, line):
 
 
 def test_gpu_bench_launches_its_own_ranks():
-    """`python3 bench.py --gpus 2` with no launcher (WORLD_SIZE unset): the script
+    """`python3 bench.py --gpus 2 --full` with no launcher (WORLD_SIZE unset): the script
     starts its two rank processes itself (bench.launch_ranks) and the caller reads
     exactly one line on stdout, the complete N = 2 line (host-staged panels, both
     ranks on this box's one GPU: ELX_BENCH_COMM=host), with the residual checked
@@ -372,7 +372,7 @@ def test_gpu_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ELX_BENCH_COMM"] = "host"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--size", "2048", "--steps", "1",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=240, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=240, env=env)
     assert p.returncode == 0, p.stdout + p.stderr[-4000:]
     lines = p.stdout.strip().splitlines()
     assert len(lines) == 1, p.stdout

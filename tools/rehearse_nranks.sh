@@ -6,4 +6,4 @@
 # usage: tools/rehearse_nranks.sh N [bench args...]
 N=$1; shift
 export ELX_BENCH_COMM=host
-python3 bench.py --gpus "$N" "$@"
+python3 bench.py --gpus "$N" --full "$@"
