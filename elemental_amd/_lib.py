@@ -79,6 +79,7 @@ _SIGS = {
     "elx_matrix_scale": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp]),
     "elx_matrix_axpy": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_copy": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "elx_matrix_trmm": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -168,6 +169,7 @@ _SIGS = {
     "elx_trrk": (_i, [_i, _i, _i, _d, _vp, _vp, _d, _vp]),
     "elx_syr2k": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_trsm": (_i, [_i, _i, _i, _i, _d, _vp, _vp, _i]),
+    "elx_trmm": (_i, [_i, _i, _i, _i, _d, _vp, _vp]),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),

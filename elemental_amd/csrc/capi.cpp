@@ -239,6 +239,33 @@ int elx_matrix_copy(int dtype, int device, int64_t m, int64_t n, const void* A, 
         exec::Copy2DBatch(d, ToDType(dtype), &c, 1, false, 0.0, DevStream(d, stream));
     });
 }
+int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int diag, int64_t m, int64_t n, double alpha,
+                    const void* A, int64_t lda, void* B, int64_t ldb, void* stream) {
+    return Guard([&] {
+        CheckOp(orient);
+        ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Trmm: bad LeftOrRight ", side);
+        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trmm: bad UpperOrLower ", uplo);
+        ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "Trmm: bad UnitOrNonUnit ", diag);
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative Trmm dimension");
+        const bool left = side == ELX_LEFT;
+        CheckLd(lda, left ? m : n, "A");
+        CheckLd(ldb, m, "B");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        if (t != DType::F64 && t != DType::F32) throw LogicError("Trmm: only float and double are supported");
+        if (m == 0 || n == 0) return;
+        hipStream_t s = DevStream(d, stream);
+        const bool lower = uplo == ELX_LOWER, trans = orient != ELX_NORMAL, unit = diag == ELX_UNIT;
+        if (left) return exec::Trmm(d, t, lower, trans, unit, m, n, alpha, A, lda, B, ldb, s);
+        // B op(A) = (op(A)^T B^T)^T through the strided-copy (transpose) kernel
+        Buffer Bt(d, (size_t)m * n * DTypeSize(t), s);
+        const kern::Copy2D to{n, m, B, ldb, 1, Bt.data(), 1, n};
+        exec::Copy2DBatch(d, t, &to, 1, false, 0.0, s);
+        exec::Trmm(d, t, lower, !trans, unit, n, m, alpha, A, lda, Bt.data(), n, s);
+        const kern::Copy2D back{m, n, Bt.data(), n, 1, B, 1, ldb};
+        exec::Copy2DBatch(d, t, &back, 1, false, 0.0, s);
+    });
+}
 
 // ---- BLAS-1 --------------------------------------------------------------
 int elx_axpy2d(int dtype, int64_t m, int64_t n, double alpha, const void* X, int64_t xcs, int64_t xrs, void* Y,
@@ -766,6 +793,12 @@ int elx_trsm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A,
     return Guard([&] {
         CheckOp(orient);
         Trsm(side, uplo, orient, diag, alpha, M(A), M(B), checkIfSingular != 0);
+    });
+}
+int elx_trmm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A, elx_dm_t B) {
+    return Guard([&] {
+        CheckOp(orient);
+        Trmm(side, uplo, orient, diag, alpha, M(A), M(B));
     });
 }
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {

@@ -394,6 +394,46 @@ void Trsm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
         cpu_trsm(lower, trans, unit, m, n, static_cast<const float*>(A), lda, static_cast<float*>(B), ldb);
 }
 
+// Reads only the stored triangle (and no diagonal when unit).  In place: with
+// op(A) lower, row i needs rows <= i of the old B, so rows go bottom to top;
+// with op(A) upper, top to bottom.
+template <typename S>
+void cpu_trmm(bool lower, bool trans, bool unit, Int m, Int n, S alpha, const S* A, Int lda, S* B, Int ldb) {
+    const bool op_lower = lower != trans;
+    auto opA = [&](Int r, Int c) { return trans ? A[c + r * lda] : A[r + c * lda]; };
+    for (Int j = 0; j < n; ++j) {
+        S* x = B + j * ldb;
+        for (Int s = 0; s < m; ++s) {
+            const Int i = op_lower ? m - 1 - s : s;
+            S acc = unit ? x[i] : opA(i, i) * x[i];
+            if (op_lower)
+                for (Int k = 0; k < i; ++k) acc += opA(i, k) * x[k];
+            else
+                for (Int k = i + 1; k < m; ++k) acc += opA(i, k) * x[k];
+            x[i] = alpha * acc;
+        }
+    }
+}
+
+void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, double alpha, const void* A, Int lda,
+          void* B, Int ldb, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("Trmm: only float and double are supported");
+    if (m <= 0 || n <= 0) return;
+    if (dev == Device::GPU) {
+        // the kernel's output may not overlap B: into a workspace, then one copy back
+        Buffer W(dev, (size_t)m * n * DTypeSize(t), s);
+        check(kern::trmm_tri((int)t, lower, trans, unit, m, n, alpha, A, lda, B, ldb, W.data(), m, s), "trmm_tri");
+        const Copy2D d{m, n, W.data(), 1, m, B, 1, ldb};
+        Copy2DBatch(dev, t, &d, 1, false, 0.0, s);
+        return;
+    }
+    if (t == DType::F64)
+        cpu_trmm(lower, trans, unit, m, n, alpha, static_cast<const double*>(A), lda, static_cast<double*>(B), ldb);
+    else
+        cpu_trmm(lower, trans, unit, m, n, (float)alpha, static_cast<const float*>(A), lda, static_cast<float*>(B),
+                 ldb);
+}
+
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,
                        hipStream_t s) {
     check(kern::tri_inverse_batched((int)t, lower, trans, unit, nb, m, A, lda, W, s), "tri_inverse_batched");

@@ -40,6 +40,9 @@ void Trapezoid(Device dev, DType t, bool lower, Int m, Int n, double alpha, cons
 // op(A) X = B in place, A m x m (LocalTrsm / blas::Trsm, Left side); f64/f32
 void Trsm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, const void* A, Int lda, void* B,
           Int ldb, hipStream_t s);
+// B := alpha * op(tri(A)) * B in place (LocalTrmm / blas::Trmm, Left side); f64/f32
+void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, double alpha, const void* A, Int lda,
+          void* B, Int ldb, hipStream_t s);
 // GPU only: W_b := op(A_bb)^-1 for every nb x nb diagonal block of the m x m A
 // (W_b at W + b*nb*nb, leading dimension nb), one launch
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,

@@ -1247,6 +1247,123 @@ void Trsm(int side, int uplo, int orient, int diag, double alpha, const DistMatr
     Transpose(*Bt, B);
 }
 
+// Trmm on DistMatrices (src/blas_like/level3/Trmm.cpp:53-89): B := alpha
+// op(tri(A)) B (LEFT) or alpha B op(tri(A)) (RIGHT), in place.  LEFT is the
+// reference's LLNC / LUNC sweep (Trmm/LLN.hpp:178-228) in the order that never
+// overwrites rows still to be read, split recursively at block boundaries as
+// TrsmLeft is: with op(A) lower,
+//   X[mid:K1] := op(A)[mid:K1, mid:K1] X[mid:K1]       (recursion)
+//   X[mid:K1] += op(A)[mid:K1, K0:mid] X[K0:mid]       (C-stationary SUMMA on views)
+//   X[K0:mid] := op(A)[K0:mid, K0:mid] X[K0:mid]       (recursion)
+// and mirrored with op(A) upper.  A leaf is one diagonal block: A11[*,*] <- A11,
+// X1[*,VR] <- X1, X1 := op(tri(A11)) X1 (trmm_tile_kernel, which skips the zero
+// half of A11), X1 <- X1[*,VR].  RIGHT runs the transposed LEFT problem through
+// two distributed transposes, as Trsm does.  f64/f32.
+void TrmmLeft(int uplo, int orient, bool unit, const DistMatrix& APre, DistMatrix& XPre) {
+    ELX_TRACE("El::Trmm");
+    MultiSync sync(XPre.Stream(), {APre.Stream()});
+    auto Ap = ReadProxy(APre, XPre, Dist::MC, Dist::MR);
+    const DistMatrix& A = *Ap;
+    RWProxy Xp(XPre);
+    DistMatrix& X = Xp.Get();
+    const Int m = X.Height(), n = X.Width();
+    Int nb = std::max<Int>(1, Blocksize());
+    const bool trans = orient != ELX_NORMAL, lower = uplo == ELX_LOWER;
+    const bool op_lower = lower != trans;
+    auto A11s = A.Like(Dist::STAR, Dist::STAR);
+    auto X1v = X.Like(Dist::STAR, Dist::VR);
+    // every operand's local block is the whole matrix (1x1 grid): updates are
+    // direct MFMA GEMMs on the local buffers, no views, proxies or pipeline
+    const bool local = SameLocalLayout(A, Dist::STAR, Dist::STAR, 0, 0) &&
+                       SameLocalLayout(X, Dist::STAR, Dist::VR, 0, X.RowAlign()) && X.LocalHeight() == m &&
+                       X.LocalWidth() == n && X.LDim() > 0;
+    // There, with the default Blocksize (128) on the GPU, the leaf is widened to
+    // ELX_TRMM_LEAF rows (default 512; 0 keeps the blocksize) once the matrix
+    // holds two of them: one triangle-aware launch that fills the chip instead
+    // of a cascade of 128-row leaves and k = 128, 256, ... updates (read per
+    // call, for A/B)
+    const char* leaf_s = getenv("ELX_TRMM_LEAF");
+    const Int leaf_env = leaf_s ? (Int)atoll(leaf_s) : (Int)512;
+    if (local && X.Dev() == Device::GPU && nb == 128 && leaf_env > nb && m >= 2 * leaf_env) nb = leaf_env;
+    if (local && X.Dev() == Device::GPU) FenceStreams(A.Stream(), X.Stream());
+    // X(r0:r1, :) += op(A)(r0:r1, k0:k1) X(k0:k1, :)
+    auto update = [&](Int r0, Int r1, Int k0, Int k1) {
+        if (r1 <= r0 || k1 <= k0 || n == 0) return;
+        if (local) {
+            const size_t es = DTypeSize(X.Type());
+            const char* a = static_cast<const char*>(A.Buffer()) +
+                            ((trans ? k0 + r0 * A.LDim() : r0 + k0 * A.LDim()) * es);
+            const char* xk = static_cast<const char*>(X.Buffer()) + k0 * es;
+            char* xr = static_cast<char*>(X.Buffer()) + r0 * es;
+            exec::Gemm(X.Dev(), X.Type(), trans, false, r1 - r0, n, k1 - k0, 1.0, a, A.LDim(), xk, X.LDim(), 1.0, xr,
+                       X.LDim(), X.Stream());
+            return;
+        }
+        auto Ar = trans ? DistMatrix::View(A, k0, k1, r0, r1) : DistMatrix::View(A, r0, r1, k0, k1);
+        auto Xk = DistMatrix::View(X, k0, k1, 0, n);
+        auto Xr = DistMatrix::View(X, r0, r1, 0, n);
+        SummaC(trans ? ELX_TRANSPOSE : ELX_NORMAL, ELX_NORMAL, 1.0, *Ar, *Xk, 1.0, *Xr);
+    };
+    // X(k0:k1, :) := op(tri(A11)) X(k0:k1, :), one diagonal block
+    auto leaf = [&](Int k0, Int k1) {
+        auto X1 = DistMatrix::View(X, k0, k1, 0, n);
+        // a block whose local storage already IS the [*,*] / [*,VR] layout (a
+        // 1x1 grid) is used in place: no redistribution temporaries
+        auto A11 = DistMatrix::View(A, k0, k1, k0, k1);
+        std::shared_ptr<const DistMatrix> a11 = A11;
+        if (!SameLocalLayout(*A11, Dist::STAR, Dist::STAR, 0, 0)) {
+            Copy(*A11, *A11s);                               // A11[*,*] <- A11[MC,MR]
+            a11 = A11s;
+        }
+        const bool inplace = SameLocalLayout(*X1, Dist::STAR, Dist::VR, 0, X1->RowAlign());
+        DistMatrix* x1 = X1.get();
+        if (!inplace) {
+            X1v->AlignRows(X.RowAlign(), true);
+            Copy(*X1, *X1v);                                 // X1[*,VR] <- X1[MC,MR]
+            x1 = X1v.get();
+        }
+        if (X.Dev() == Device::GPU) FenceStreams(a11->Stream(), x1->Stream());
+        exec::Trmm(X.Dev(), X.Type(), lower, trans, unit, k1 - k0, x1->LocalWidth(), 1.0, a11->Buffer(), a11->LDim(),
+                   x1->Buffer(), x1->LDim(), x1->Stream());
+        if (!inplace) Copy(*X1v, *X1);                       // X1[MC,MR] <- X1[*,VR]
+    };
+    std::function<void(Int, Int)> mul = [&](Int K0, Int K1) {
+        const Int nbk = (K1 - K0 + nb - 1) / nb;
+        if (nbk <= 1) return leaf(K0, K1);
+        const Int mid = K0 + (nbk / 2) * nb;
+        if (op_lower) {
+            mul(mid, K1);
+            update(mid, K1, K0, mid);
+            mul(K0, mid);
+        } else {
+            mul(K0, mid);
+            update(K0, mid, mid, K1);
+            mul(mid, K1);
+        }
+    };
+    if (m > 0 && n > 0) mul(0, m);
+    Xp.Finish();
+}
+
+void Trmm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B) {
+    ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Trmm: bad LeftOrRight ", side);
+    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trmm: bad UpperOrLower ", uplo);
+    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "Trmm: bad orientation");
+    ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "Trmm: bad UnitOrNonUnit ", diag);
+    ELX_REQUIRE(&A.G() == &B.G(), "Trmm: matrices on different grids");
+    ELX_REQUIRE(A.Type() == B.Type(), "Trmm: mixed types");
+    if (A.Type() != DType::F64 && A.Type() != DType::F32) throw LogicError("Trmm: only float and double are supported");
+    if (A.Height() != A.Width()) throw LogicError("Triangular matrix must be square");  // Trmm.cpp:31-32
+    if ((side == ELX_LEFT ? B.Height() : B.Width()) != A.Height()) throw LogicError("Nonconformal Trmm");
+    Scale(alpha, B);  // Trmm.cpp:60 (X *= alpha)
+    if (side == ELX_LEFT) return TrmmLeft(uplo, orient, diag == ELX_UNIT, A, B);
+    // B op(A) = (op(A)^T B^T)^T
+    auto Bt = B.Like(Dist::MC, Dist::MR);
+    Transpose(B, *Bt);
+    TrmmLeft(uplo, orient == ELX_NORMAL ? ELX_TRANSPOSE : ELX_NORMAL, diag == ELX_UNIT, A, *Bt);
+    Transpose(*Bt, B);
+}
+
 // Symm / Hemm on DistMatrices (src/blas_like/level3/Symm.cpp:55-80): C := alpha
 // A B + beta C (LEFT) or alpha B A + beta C (RIGHT), A symmetric with only its
 // uplo triangle read.  The reference accumulates triangle-aware local products

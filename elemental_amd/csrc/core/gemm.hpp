@@ -28,6 +28,8 @@ void Syr2k(int uplo, int orient, double alpha, const DistMatrix& A, const DistMa
 // checkIfSingular: SingularMatrixError when a NON_UNIT diagonal holds an exact zero (Trsm.cpp:60-68)
 void Trsm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B,
           bool checkIfSingular = false);
+// B := alpha op(tri(A)) B (LEFT) / alpha B op(tri(A)) (RIGHT)  (Trmm.cpp:53-89)
+void Trmm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B);
 // C := alpha A B + beta C (LEFT) / alpha B A + beta C (RIGHT), A symmetric (uplo stored)  (Symm.cpp:55-80)
 void Symm(int side, int uplo, double alpha, const DistMatrix& A, const DistMatrix& B, double beta, DistMatrix& C);
 

@@ -288,5 +288,21 @@ constexpr long kTriInverseLdsMax = 150 * 1024;
 bool tri_inverse_lds_ok(int dtype, i64 nb);
 hipError_t tri_inverse_batched(int dtype, bool lower, bool trans, bool unit, i64 nb, i64 m, const void* A, i64 lda,
                                void* W, hipStream_t s);
+// C := alpha * op(tri(A)) * B.  A is m x m, only its uplo triangle is read
+// (unit: the diagonal is not read either and counts as 1).  B and C are m x n,
+// C must not overlap B.  f64 / f32.
+hipError_t trmm_tri(int dtype, bool lower, bool trans, bool unit, i64 m, i64 n, double alpha, const void* A, i64 lda,
+                    const void* B, i64 ldb, void* C, i64 ldc, hipStream_t s);
+// trmm_tri's tiling: rows per output tile (f64 / f32) and the k-slab depth
+constexpr int kTrmmBM64 = 128, kTrmmBM32 = 256, kTrmmBK = 16;
+// The k range [k0, k1) that the output row tile [i0, i0 + bm) of trmm_tri
+// walks, in slabs of bk from k0 (a multiple of bk; i0 is a multiple of bm and
+// bm of bk).  op_lower = (lower != trans): op(A)(i,k) is stored for k <= i,
+// else for k >= i.  Here (and constexpr, so the kernel calls the same code) so
+// tests/cpp/test_trmm_plan.cpp checks it without a GPU.
+struct TrmmKRange { i64 k0, k1; };
+constexpr TrmmKRange trmm_krange(bool op_lower, i64 m, i64 i0, i64 bm, i64 bk = kTrmmBK) {
+    return op_lower ? TrmmKRange{0, i0 + bm < m ? i0 + bm : m} : TrmmKRange{i0 / bk * bk, m};
+}
 }  // namespace kern
 }  // namespace elx

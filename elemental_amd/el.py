@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -353,6 +353,13 @@ def Trsm(side, uplo, orientation, diag, alpha, A: DistMatrix, B: DistMatrix, che
     B is overwritten with alpha op(A)^-1 B (LEFT) or alpha B op(A)^-1 (RIGHT);
     checkIfSingular raises SingularMatrixError on an exact zero NON_UNIT diagonal."""
     call("elx_trsm", side, uplo, orientation, diag, float(alpha), A.h, B.h, int(bool(checkIfSingular)))
+
+
+def Trmm(side, uplo, orientation, diag, alpha, A: DistMatrix, B: DistMatrix):
+    """El::Trmm(side, uplo, orientation, diag, alpha, A, B) (Trmm.cpp:53-89): B is
+    overwritten with alpha op(tri(A)) B (LEFT) or alpha B op(tri(A)) (RIGHT); only
+    A's uplo triangle is read (and no diagonal when UNIT)."""
+    call("elx_trmm", side, uplo, orientation, diag, float(alpha), A.h, B.h)
 
 
 def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, conjugate: bool = False):

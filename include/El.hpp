@@ -975,6 +975,50 @@ void Trsm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNo
     detail::Check(elx_trsm(side, uplo, orientation, diag, detail::ToDouble(alpha), A.h(), B.h(),
                            checkIfSingular ? 1 : 0));
 }
+// Trmm (src/blas_like/level3/Trmm.cpp): B := alpha op(tri(A)) B (LEFT) or alpha B
+// op(tri(A)) (RIGHT) in place; only A's uplo triangle is read.  float and double.
+// On local matrices (Trmm.cpp:23-51): the triangle-aware MFMA kernel on the GPU
+// (on B's stream), the library's host loop on the CPU
+template <typename T>
+void Trmm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+          const AbstractMatrix<T>& A, AbstractMatrix<T>& B) {
+    if (A.GetDevice() != B.GetDevice()) throw LogicError("Trmm: A and B must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("Triangular matrix must be square");
+    if (A.Height() != (side == LEFT ? B.Height() : B.Width())) throw LogicError("Nonconformal Trmm");
+    detail::LocalFence<T> fence(B, {&A});
+    detail::Check(elx_matrix_trmm(detail::TypeCode<T>::value, static_cast<int>(B.GetDevice()), side, uplo, orientation,
+                                  diag, B.Height(), B.Width(), detail::ToDouble(alpha), A.LockedBuffer(), A.LDim(),
+                                  B.Buffer(), B.LDim(), B.Stream()));
+}
+template <typename T, Device D>
+void Trmm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+          const Matrix<T, D>& A, Matrix<T, D>& B) {
+    Trmm(side, uplo, orientation, diag, alpha, static_cast<const AbstractMatrix<T>&>(A),
+         static_cast<AbstractMatrix<T>&>(B));
+}
+// on DistMatrices (Trmm.cpp:53-89)
+template <typename T>
+void Trmm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+          const AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& B) {
+    detail::Check(elx_trmm(side, uplo, orientation, diag, detail::ToDouble(alpha), A.h(), B.h()));
+}
+// on the local blocks (Trmm.cpp:91-106): A is [*,*], and so is the dimension of
+// B that meets the triangle
+template <typename T, Device D>
+void LocalTrmm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+               const DistMatrix<T, STAR, STAR, ELEMENT, D>& A, AbstractDistMatrix<T>& B) {
+    if ((side == LEFT && B.ColDist() != STAR) || (side == RIGHT && B.RowDist() != STAR))
+        throw LogicError("Dist of RHS must conform with that of triangle");
+    if (B.GetLocalDevice() != D) throw LogicError("LocalTrmm: A and B must be on the same device");
+    if (A.Height() != (side == LEFT ? B.Height() : B.Width())) throw LogicError("Nonconformal Trmm");
+    // A's queued work lands before B's stream reads it, and B's is done with A on return
+    const bool fence = D == Device::GPU && A.Stream() != B.Stream();
+    if (fence) A.Synchronize();
+    detail::Check(elx_matrix_trmm(detail::TypeCode<T>::value, static_cast<int>(D), side, uplo, orientation, diag,
+                                  B.LocalHeight(), B.LocalWidth(), detail::ToDouble(alpha), A.LockedBuffer(),
+                                  A.LDim() > 1 ? A.LDim() : 1, B.Buffer(), B.LDim() > 1 ? B.LDim() : 1, B.Stream()));
+    if (fence) B.Synchronize();
+}
 template <typename T>
 void Symm(LeftOrRight side, UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& B,
           T beta, AbstractDistMatrix<T>& C, bool conjugate = false) {

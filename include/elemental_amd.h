@@ -194,6 +194,12 @@ int elx_matrix_axpy(int dtype, int device, int64_t m, int64_t n, double alpha,
                     const void* X, int64_t ldx, void* Y, int64_t ldy, void* stream);
 int elx_matrix_copy(int dtype, int device, int64_t m, int64_t n, const void* A, int64_t lda,
                     void* B, int64_t ldb, void* stream);
+/* El::Trmm on Matrix<T> (src/blas_like/level3/Trmm.cpp:23-51): B (m x n) := alpha
+ * op(tri(A)) B (LEFT, A m x m) or alpha B op(tri(A)) (RIGHT, A n x n), in place;
+ * only A's uplo triangle is read (and no diagonal when UNIT).  f32/f64. */
+int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int diag,
+                    int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
+                    void* B, int64_t ldb, void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -476,6 +482,9 @@ int elx_syr2k(int uplo, int orient, double alpha, elx_dm_t A, elx_dm_t B, double
  * op(A)^-1 B (ELX_LEFT) or alpha B op(A)^-1 (ELX_RIGHT); float and double */
 int elx_trsm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A, elx_dm_t B,
              int checkIfSingular);  /* ELX_ERR_SINGULAR on an exact zero NON_UNIT diagonal (Trsm.cpp:60-68) */
+/* El::Trmm on DistMatrices (src/blas_like/level3/Trmm.cpp:53-89): B := alpha
+ * op(tri(A)) B (ELX_LEFT) or alpha B op(tri(A)) (ELX_RIGHT), in place; float and double */
+int elx_trmm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A, elx_dm_t B);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
