@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libelemental_amd.so")
 
 # status codes / enums (mirrors include/elemental_amd.h)
 OK, ERR_LOGIC, ERR_HIP, ERR_COMM, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_SINGULAR = range(8)
+ERR_NOT_HPD = 8
 NORMAL, TRANSPOSE, ADJOINT = 0, 1, 2
 MC, MD, MR, VC, VR, STAR, CIRC = range(7)
 (GEMM_DEFAULT, GEMM_SUMMA_A_MS, GEMM_SUMMA_A, GEMM_SUMMA_B_MS, GEMM_SUMMA_B, GEMM_SUMMA_C_MS,
@@ -41,6 +42,7 @@ HOST_SPLIT_FN = CFUNCTYPE(c_int, c_void_p, c_int, c_int, c_int, POINTER(c_int), 
 _vp, _i, _i64, _d = c_void_p, c_int, c_int64, c_double
 _SIGS = {
     "elx_last_error": (c_char_p, []),
+    "elx_last_nonhpd_column": (_i, []),
     "elx_version": (_i, []),
     "elx_device_count": (_i, [POINTER(c_int)]),
     "elx_set_device": (_i, [_i]),
@@ -80,6 +82,7 @@ _SIGS = {
     "elx_matrix_axpy": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_copy": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_trmm": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
+    "elx_matrix_cholesky": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -170,6 +173,9 @@ _SIGS = {
     "elx_syr2k": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_trsm": (_i, [_i, _i, _i, _i, _d, _vp, _vp, _i]),
     "elx_trmm": (_i, [_i, _i, _i, _i, _d, _vp, _vp]),
+    "elx_cholesky": (_i, [_i, _vp]),
+    "elx_cholesky_leaf_max": (_i64, []),
+    "elx_cholesky_solve_after": (_i, [_i, _i, _vp, _vp]),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),
@@ -215,8 +221,17 @@ class SingularMatrixError(ElxError):
     """El::SingularMatrixException (include/El/core/environment/decl.hpp:209-214)."""
 
 
+class NonHPDMatrixError(ElxError):
+    """El::NonHPDMatrixException (include/El/core/environment/decl.hpp:226-231);
+    `column` is the 1-based column of the first pivot that was not > 0."""
+
+    def __init__(self, code: int, msg: str):
+        super().__init__(code, msg)
+        self.column = int(lib().elx_last_nonhpd_column())
+
+
 _EXC = {ERR_LOGIC: LogicError, ERR_UNSUPPORTED: UnsupportedError, ERR_NO_DEVICE: NoDeviceError,
-        ERR_SINGULAR: SingularMatrixError}
+        ERR_SINGULAR: SingularMatrixError, ERR_NOT_HPD: NonHPDMatrixError}
 
 _lib = None
 

@@ -43,6 +43,8 @@ elx_comm_s& WorldHandle() {
 }  // namespace
 
 void SetLastError(const std::string& msg) { g_last_error = msg; }
+thread_local int g_last_nonhpd_column = 0;
+void SetLastNonHPDColumn(int col) { g_last_nonhpd_column = col; }
 }  // namespace elx
 
 using namespace elx;
@@ -50,6 +52,7 @@ using namespace elx;
 extern "C" {
 
 const char* elx_last_error(void) { return g_last_error.c_str(); }
+int elx_last_nonhpd_column(void) { return g_last_nonhpd_column; }
 int elx_version(void) { return 10000; }
 
 int elx_device_count(int* count) {
@@ -264,6 +267,25 @@ int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int d
         exec::Trmm(d, t, lower, !trans, unit, n, m, alpha, A, lda, Bt.data(), n, s);
         const kern::Copy2D back{m, n, Bt.data(), n, 1, B, 1, ldb};
         exec::Copy2DBatch(d, t, &back, 1, false, 0.0, s);
+    });
+}
+
+int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
+    return Guard([&] {
+        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Cholesky: bad UpperOrLower ", uplo);
+        ELX_REQUIRE(n >= 0, "negative Cholesky dimension");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        if (t != DType::F64 && t != DType::F32) throw LogicError("Cholesky: only float and double are supported");
+        CheckLd(lda, n, "A");
+        if (n == 0) return;
+        // the buffer as the local block of a 1x1-grid [MC,MR] matrix: a large
+        // Matrix gets the blocked driver, not one leaf
+        static const auto grid = std::make_shared<Grid>(Comm::Self(), 1, ELX_COLUMN_MAJOR);
+        DistMatrix M(grid, t, Dist::MC, Dist::MR, d);
+        M.Attach(n, n, 0, 0, A, lda, 0);
+        if (d == Device::GPU) M.SetStream(DevStream(d, stream));
+        Cholesky(uplo, M);
     });
 }
 
@@ -799,6 +821,15 @@ int elx_trmm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A,
     return Guard([&] {
         CheckOp(orient);
         Trmm(side, uplo, orient, diag, alpha, M(A), M(B));
+    });
+}
+int64_t elx_cholesky_leaf_max(void) { return kern::kPotrfMax; }
+int elx_cholesky(int uplo, elx_dm_t A) { return Guard([&] { Cholesky(uplo, M(A)); }); }
+int elx_cholesky_solve_after(int uplo, int orient, elx_dm_t A, elx_dm_t B) {
+    return Guard([&] {
+        CheckOp(orient);
+        ELX_REQUIRE(&M(A).G() == &M(B).G(), "SolveAfter: matrices on different grids");
+        cholesky::SolveAfter(uplo, orient, M(A), M(B));
     });
 }
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {

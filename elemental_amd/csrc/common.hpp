@@ -26,6 +26,13 @@ struct NoDeviceError : std::runtime_error { using std::runtime_error::runtime_er
 struct SingularMatrixError : std::runtime_error {
     SingularMatrixError() : std::runtime_error("Matrix was singular") {}
 };
+// El::NonHPDMatrixException (include/El/core/environment/decl.hpp); column: the
+// 1-based column whose pivot was not positive
+struct NonHPDMatrixError : std::runtime_error {
+    explicit NonHPDMatrixError(int col)
+        : std::runtime_error("A was not numerically HPD"), column(col) {}
+    int column;
+};
 
 template <typename... Args>
 std::string Cat(Args&&... args) {
@@ -48,6 +55,7 @@ std::string Cat(Args&&... args) {
     do { if (!(cond)) throw ::elx::LogicError(::elx::Cat(__VA_ARGS__)); } while (0)
 
 void SetLastError(const std::string& msg);
+void SetLastNonHPDColumn(int col);  // read back with elx_last_nonhpd_column()
 
 // Run `f`, translating exceptions into C-ABI status codes.
 template <typename F>
@@ -61,6 +69,11 @@ int Guard(F&& f) {
     catch (const CommError& e)          { SetLastError(e.what()); return ELX_ERR_COMM; }
     catch (const NoDeviceError& e)      { SetLastError(e.what()); return ELX_ERR_NO_DEVICE; }
     catch (const SingularMatrixError& e) { SetLastError(e.what()); return ELX_ERR_SINGULAR; }
+    catch (const NonHPDMatrixError& e) {
+        SetLastError(e.what());
+        SetLastNonHPDColumn(e.column);
+        return ELX_ERR_NOT_HPD;
+    }
     catch (const std::logic_error& e)   { SetLastError(e.what()); return ELX_ERR_LOGIC; }
     catch (const std::exception& e)     { SetLastError(e.what()); return ELX_ERR_RUNTIME; }
     catch (...)                         { SetLastError("unknown exception"); return ELX_ERR_RUNTIME; }

@@ -434,6 +434,38 @@ void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
                  ldb);
 }
 
+// LowerVariant3Unblocked (LowerVariant3.hpp:24-50) on the stored triangle:
+// S(i,j), i >= j, is A(i,j) when lower and A(j,i) when upper (A = U^T U)
+template <typename S>
+void cpu_cholesky(bool lower, Int n, S* A, Int lda, int* info, int col0) {
+    auto a = [&](Int i, Int j) -> S& { return lower ? A[i + j * lda] : A[j + i * lda]; };
+    for (Int j = 0; j < n; ++j) {
+        const S d = a(j, j);
+        if (!(d > S(0))) {
+            if (*info == 0) *info = col0 + (int)j + 1;
+            return;
+        }
+        const S sd = std::sqrt(d), inv = S(1) / sd;
+        a(j, j) = sd;
+        for (Int i = j + 1; i < n; ++i) a(i, j) *= inv;
+        for (Int k = j + 1; k < n; ++k)
+            for (Int i = k; i < n; ++i) a(i, k) -= a(i, j) * a(k, j);
+    }
+}
+
+void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* info, int col0, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("Cholesky: only float and double are supported");
+    if (n <= 0) return;
+    if (dev == Device::GPU) {
+        ELX_REQUIRE(n <= kern::kPotrfMax, "Cholesky: block of ", n, " rows exceeds ", kern::kPotrfMax);
+        check(kern::potrf_block((int)t, lower, n, A, lda, info, col0, s), "potrf_block");
+        return;
+    }
+    if (*info != 0) return;
+    if (t == DType::F64) cpu_cholesky(lower, n, static_cast<double*>(A), lda, info, col0);
+    else cpu_cholesky(lower, n, static_cast<float*>(A), lda, info, col0);
+}
+
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,
                        hipStream_t s) {
     check(kern::tri_inverse_batched((int)t, lower, trans, unit, nb, m, A, lda, W, s), "tri_inverse_batched");

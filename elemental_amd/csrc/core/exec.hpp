@@ -43,6 +43,12 @@ void Trsm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
 // B := alpha * op(tri(A)) * B in place (LocalTrmm / blas::Trmm, Left side); f64/f32
 void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, double alpha, const void* A, Int lda,
           void* B, Int ldb, hipStream_t s);
+// A = L L^T (lower) / U^T U in place on the uplo triangle of the n x n A, n <=
+// kern::kPotrfMax on the GPU (LowerVariant3Unblocked, LowerVariant3.hpp:17-50).
+// A pivot that is not > 0 stops it and stores col0 + j + 1 in *info if that is
+// still 0; a non-zero *info on entry makes the call a no-op.  info is device
+// memory for Device::GPU, host memory for Device::CPU.  f64/f32
+void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* info, int col0, hipStream_t s);
 // GPU only: W_b := op(A_bb)^-1 for every nb x nb diagonal block of the m x m A
 // (W_b at W + b*nb*nb, leading dimension nb), one launch
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,

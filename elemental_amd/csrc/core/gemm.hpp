@@ -30,6 +30,13 @@ void Trsm(int side, int uplo, int orient, int diag, double alpha, const DistMatr
           bool checkIfSingular = false);
 // B := alpha op(tri(A)) B (LEFT) / alpha B op(tri(A)) (RIGHT)  (Trmm.cpp:53-89)
 void Trmm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B);
+// A = L L^T (LOWER) / U^T U (UPPER) in place on the uplo triangle; NonHPDMatrixError
+// with the 1-based column of the first pivot that is not > 0  (Cholesky/LowerVariant3.hpp:78-134)
+void Cholesky(int uplo, DistMatrix& A);
+namespace cholesky {
+// B := A^-1 B from the factor in A's uplo triangle  (Cholesky/SolveAfter.hpp:78-107)
+void SolveAfter(int uplo, int orient, const DistMatrix& A, DistMatrix& B);
+}  // namespace cholesky
 // C := alpha A B + beta C (LEFT) / alpha B A + beta C (RIGHT), A symmetric (uplo stored)  (Symm.cpp:55-80)
 void Symm(int side, int uplo, double alpha, const DistMatrix& A, const DistMatrix& B, double beta, DistMatrix& C);
 

@@ -304,5 +304,13 @@ struct TrmmKRange { i64 k0, k1; };
 constexpr TrmmKRange trmm_krange(bool op_lower, i64 m, i64 i0, i64 bm, i64 bk = kTrmmBK) {
     return op_lower ? TrmmKRange{0, i0 + bm < m ? i0 + bm : m} : TrmmKRange{i0 / bk * bk, m};
 }
+// Cholesky of one n x n block in place, n <= kPotrfMax (one workgroup, the block
+// held in LDS; 128: f64 128 x 129 x 8 B = 129 KiB of gfx950's 160 KiB).  Only the
+// uplo triangle of A is read and written.  A pivot that is not > 0 (NaN
+// included) stops the factorization and stores col0 + j + 1 (1-based column) in
+// the device word *info if it is still 0; a launch that finds *info != 0 does
+// nothing.  f64 / f32.
+constexpr i64 kPotrfMax = 128;
+hipError_t potrf_block(int dtype, bool lower, i64 n, void* A, i64 lda, int* info, int col0, hipStream_t s);
 }  // namespace kern
 }  // namespace elx

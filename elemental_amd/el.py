@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -360,6 +360,23 @@ def Trmm(side, uplo, orientation, diag, alpha, A: DistMatrix, B: DistMatrix):
     overwritten with alpha op(tri(A)) B (LEFT) or alpha B op(tri(A)) (RIGHT); only
     A's uplo triangle is read (and no diagonal when UNIT)."""
     call("elx_trmm", side, uplo, orientation, diag, float(alpha), A.h, B.h)
+
+
+NonHPDMatrixError = L.NonHPDMatrixError
+
+
+def Cholesky(uplo, A: DistMatrix):
+    """El::Cholesky(uplo, A) (Cholesky/LowerVariant3.hpp:78-134): A is overwritten
+    on its uplo triangle with its Cholesky factor (A = L L^T for LOWER, U^T U for
+    UPPER); the other triangle is neither read nor written.  Raises
+    NonHPDMatrixError (on every rank; `.column` is 1-based) when a pivot is not > 0."""
+    call("elx_cholesky", uplo, A.h)
+
+
+def CholeskySolveAfter(uplo, orientation, A: DistMatrix, B: DistMatrix):
+    """El::cholesky::SolveAfter(uplo, orientation, A, B) (Cholesky/SolveAfter.hpp:
+    78-107): B := A^-1 B from the factor El::Cholesky left in A's uplo triangle."""
+    call("elx_cholesky_solve_after", uplo, orientation, A.h, B.h)
 
 
 def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, conjugate: bool = False):

@@ -234,6 +234,17 @@ struct SingularMatrixException : std::runtime_error {
     explicit SingularMatrixException(const char* msg = "Matrix was singular") : std::runtime_error(msg) {}
 };
 
+// include/El/core/environment/decl.hpp:226-231; Column(): the 1-based column of the
+// first pivot that was not > 0
+struct NonHPDMatrixException : std::runtime_error {
+    explicit NonHPDMatrixException(const char* msg = "Matrix was not HPD", int column = 0)
+        : std::runtime_error(msg), column_(column) {}
+    int Column() const noexcept { return column_; }
+
+private:
+    int column_;
+};
+
 namespace detail {
 // rc's exception; `msg` when the library's last error was overwritten since
 inline void Check(int rc, const std::string& saved = std::string()) {
@@ -245,6 +256,7 @@ inline void Check(int rc, const std::string& saved = std::string()) {
     case ELX_ERR_HIP:
     case ELX_ERR_NO_DEVICE: throw hydrogen::GPUError(msg);
     case ELX_ERR_SINGULAR: throw SingularMatrixException(msg.c_str());
+    case ELX_ERR_NOT_HPD: throw NonHPDMatrixException(msg.c_str(), elx_last_nonhpd_column());
     default: throw RuntimeError(msg);
     }
 }
@@ -1018,6 +1030,51 @@ void LocalTrmm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, Uni
                                   B.LocalHeight(), B.LocalWidth(), detail::ToDouble(alpha), A.LockedBuffer(),
                                   A.LDim() > 1 ? A.LDim() : 1, B.Buffer(), B.LDim() > 1 ? B.LDim() : 1, B.Stream()));
     if (fence) B.Synchronize();
+}
+// Cholesky (src/lapack_like/factor/Cholesky.cpp): A := its Cholesky factor in place
+// on the uplo triangle (A = L L^T for LOWER, U^T U for UPPER); the other triangle
+// is neither read nor written.  NonHPDMatrixException when a pivot is not > 0
+// (thrown on every rank).  float and double.  On a DistMatrix the recursive
+// blocked driver (Cholesky/LowerVariant3.hpp:78-134); a Matrix runs the same
+// driver on its buffer (on A's stream, which is synchronized: the status has
+// to be read back)
+template <typename T>
+void Cholesky(UpperOrLower uplo, AbstractDistMatrix<T>& A) {
+    detail::Check(elx_cholesky(uplo, A.h()));
+}
+template <typename T>
+void Cholesky(UpperOrLower uplo, AbstractMatrix<T>& A) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_cholesky(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, A.Height(),
+                                      A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void Cholesky(UpperOrLower uplo, Matrix<T, D>& A) {
+    Cholesky(uplo, static_cast<AbstractMatrix<T>&>(A));
+}
+namespace cholesky {
+// B := A^-1 B from the factor in A's uplo triangle (Cholesky/SolveAfter.hpp:78-107)
+template <typename T>
+void SolveAfter(UpperOrLower uplo, Orientation orientation, const AbstractDistMatrix<T>& A,
+                AbstractDistMatrix<T>& B) {
+    detail::Check(elx_cholesky_solve_after(uplo, orientation, A.h(), B.h()));
+}
+}  // namespace cholesky
+namespace hpd_solve {
+// A := its factor, B := A^-1 B (src/lapack_like/solve/HPD.cpp:27-43)
+template <typename T>
+void Overwrite(UpperOrLower uplo, Orientation orientation, AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& B) {
+    Cholesky(uplo, A);
+    cholesky::SolveAfter(uplo, orientation, A, B);
+}
+}  // namespace hpd_solve
+// B := A^-1 B, A Hermitian positive-definite with its uplo triangle stored; A is
+// factored in a copy (HPD.cpp:59-70)
+template <typename T, Dist U, Dist V, Device D>
+void HPDSolve(UpperOrLower uplo, Orientation orientation, const DistMatrix<T, U, V, ELEMENT, D>& A,
+              AbstractDistMatrix<T>& B) {
+    DistMatrix<T, MC, MR, ELEMENT, D> ACopy(A);
+    hpd_solve::Overwrite(uplo, orientation, ACopy, B);
 }
 template <typename T>
 void Symm(LeftOrRight side, UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& B,

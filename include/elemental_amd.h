@@ -29,6 +29,7 @@ extern "C" {
 #define ELX_ERR_UNSUPPORTED     5  /* "Bad device/type combo" LogicErrors        */
 #define ELX_ERR_NO_DEVICE       6  /* no gfx950 device visible                   */
 #define ELX_ERR_SINGULAR        7  /* El::SingularMatrixException                */
+#define ELX_ERR_NOT_HPD         8  /* El::NonHPDMatrixException (elx_last_nonhpd_column) */
 
 /* ---- enums: ordinals match the reference ------------------------------- */
 /* El::Orientation  include/El/core/types.hpp:463-469 */
@@ -104,6 +105,8 @@ extern "C" {
 /* ---- errors / runtime --------------------------------------------------- */
 /* replaces hydrogen::HIPError / H_CHECK_HIP (include/hydrogen/device/gpu/rocm/ROCmError.hpp) */
 const char* elx_last_error(void);
+/* after ELX_ERR_NOT_HPD on this thread: the 1-based column of the first pivot that was not > 0 */
+int elx_last_nonhpd_column(void);
 int elx_version(void);
 /* replaces hydrogen::gpu::Initialize / ComputeDeviceId (src/hydrogen/device/GPU.cpp:30-67) */
 int elx_device_count(int* count);
@@ -200,6 +203,12 @@ int elx_matrix_copy(int dtype, int device, int64_t m, int64_t n, const void* A, 
 int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int diag,
                     int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
                     void* B, int64_t ldb, void* stream);
+/* El::Cholesky on Matrix<T> (src/lapack_like/factor/Cholesky.cpp): the n x n A :=
+ * its Cholesky factor, in place on the uplo triangle (A = L L^T for ELX_LOWER, U^T U
+ * for ELX_UPPER); the other triangle is neither read nor written.  Runs the blocked
+ * driver of elx_cholesky on the buffer.  ELX_ERR_NOT_HPD when a pivot is not > 0.
+ * Synchronizes the stream (the status has to be read back).  f32/f64. */
+int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -485,6 +494,16 @@ int elx_trsm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A,
 /* El::Trmm on DistMatrices (src/blas_like/level3/Trmm.cpp:53-89): B := alpha
  * op(tri(A)) B (ELX_LEFT) or alpha B op(tri(A)) (ELX_RIGHT), in place; float and double */
 int elx_trmm(int side, int uplo, int orient, int diag, double alpha, elx_dm_t A, elx_dm_t B);
+/* El::Cholesky on a DistMatrix (src/lapack_like/factor/Cholesky/LowerVariant3.hpp:78-134):
+ * A := its Cholesky factor in place on the uplo triangle; ELX_ERR_NOT_HPD (on every
+ * rank) when a pivot is not > 0; float and double */
+int elx_cholesky(int uplo, elx_dm_t A);
+/* the largest diagonal block one leaf kernel factors (kPotrfMax): elx_cholesky blocks by
+ * min(Blocksize(), this) */
+int64_t elx_cholesky_leaf_max(void);
+/* El::cholesky::SolveAfter (Cholesky/SolveAfter.hpp:78-107): B := A^-1 B from the
+ * factor that elx_cholesky left in A's uplo triangle */
+int elx_cholesky_solve_after(int uplo, int orient, elx_dm_t A, elx_dm_t B);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
