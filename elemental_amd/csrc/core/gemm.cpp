@@ -25,17 +25,17 @@
 //    its own stream and duplicated RCCL communicators (SummaCMultistream,
 //    SummaA/SummaB with teams); NT/TN included (the reference's ROCm build
 //    rejects those, TN.hpp:124-128).
-#include "gemm.hpp"
+#include "level3_internal.hpp"
 #include <cstdlib>
-#include "redist.hpp"
 #include "exec.hpp"
 #include <algorithm>
 #include <functional>
 #include "../runtime/trace.hpp"
-#include <initializer_list>
 #include <vector>
 
 namespace elx {
+
+using namespace detail;
 
 namespace {
 // the algorithmic blocksize stack (src/blas_like/blocksizes.cpp:16,38-72);
@@ -58,8 +58,6 @@ Int DotBlockGPU() {  // ELX_DOT_BLOCK overrides (tuning experiments)
     static const Int v = [] { const char* e = getenv("ELX_DOT_BLOCK"); return e ? (Int)atoll(e) : kDotBlockGPU; }();
     return v;
 }
-
-bool IsN(int o) { return o == ELX_NORMAL; }
 
 // Event-bracketed profiling of the local updates and panel transfers.
 struct Profiler {
@@ -91,84 +89,6 @@ Profiler& Prof() {
     static Profiler p;
     return p;
 }
-
-void FenceStreams(hipStream_t from, hipStream_t to) {
-    if (!from || !to || from == to) return;
-    hipEvent_t ev;
-    ELX_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    ELX_CHECK_HIP(hipEventRecord(ev, from));
-    ELX_CHECK_HIP(hipStreamWaitEvent(to, ev, 0));
-    ELX_CHECK_HIP(hipEventDestroy(ev));
-}
-
-// MultiSync (include/hydrogen/MultiSync.hpp:33-78): on entry the master stream
-// waits for the others' queued work; on exit the others wait for the master, so
-// a caller that reuses A or B on its own stream, and every temporary released
-// on those streams, is ordered after the reads issued here.
-class MultiSync {
-public:
-    MultiSync(hipStream_t master, std::initializer_list<hipStream_t> others) : master_(master), others_(others) {
-        for (hipStream_t o : others_) FenceStreams(o, master_);
-    }
-    ~MultiSync() {
-        for (hipStream_t o : others_) {
-            try { FenceStreams(master_, o); } catch (...) {}
-        }
-    }
-    MultiSync(const MultiSync&) = delete;
-    MultiSync& operator=(const MultiSync&) = delete;
-
-private:
-    hipStream_t master_;
-    std::vector<hipStream_t> others_;
-};
-
-// DistMatrixReadProxy<T,T,cd,rd,ELEMENT,D> (include/El/core/Proxy.hpp:174-300):
-// the operands are brought to the device of `tgt` (the matrix being written,
-// as Gemm/NN.hpp:357-359 proxies A and B onto C's device) and every read is
-// queued on tgt's stream.  A itself (as a view on that stream) when it already
-// has dist (cd,rd), that device [and the requested alignment]; else a
-// redistributed copy, moved across devices when needed.
-std::shared_ptr<const DistMatrix> ReadProxy(const DistMatrix& A, const DistMatrix& tgt, Dist cd, Dist rd,
-                                            int calign = -1, int ralign = -1) {
-    const bool ok = A.Dev() == tgt.Dev() && A.ColDist() == cd && A.RowDist() == rd &&
-                    (calign < 0 || A.ColAlign() == calign) && (ralign < 0 || A.RowAlign() == ralign);
-    if (ok) {
-        if (A.Dev() != Device::GPU || A.Stream() == tgt.Stream())
-            return std::shared_ptr<const DistMatrix>(&A, [](const DistMatrix*) {});
-        auto V = DistMatrix::View(A, 0, A.Height(), 0, A.Width());
-        V->SetStream(tgt.Stream());
-        return V;
-    }
-    auto T = A.LikeOn(cd, rd, tgt.Dev());
-    T->SetStream(tgt.Stream());
-    // A's local block already holds exactly the (cd,rd) block on every rank
-    // (e.g. [MC,MR] -> [VC,*] on a 1x1 grid): relabel it in place, no copy
-    const int ca = calign >= 0 ? calign : 0, ra = ralign >= 0 ? ralign : 0;
-    if (A.Dev() == tgt.Dev() && A.Root() == 0 && SameLocalLayout(A, cd, rd, ca, ra)) {
-        T->Attach(A.Height(), A.Width(), ca, ra, const_cast<void*>(A.Buffer()), A.LDim(), 0);
-        if (A.Dev() == Device::GPU) FenceStreams(A.Stream(), tgt.Stream());
-        return T;
-    }
-    if (calign >= 0) T->AlignCols(calign, true);
-    if (ralign >= 0) T->AlignRows(ralign, true);
-    Copy(A, *T);
-    return T;
-}
-
-// DistMatrixReadWriteProxy for C: work in [MC,MR]; copy back on Finish().
-struct RWProxy {
-    DistMatrix& orig;
-    std::shared_ptr<DistMatrix> tmp;
-    explicit RWProxy(DistMatrix& C) : orig(C) {
-        if (C.ColDist() != Dist::MC || C.RowDist() != Dist::MR) {
-            tmp = C.Like(Dist::MC, Dist::MR);
-            Copy(C, *tmp);
-        }
-    }
-    DistMatrix& Get() { return tmp ? *tmp : orig; }
-    void Finish() { if (tmp) Copy(*tmp, orig); }
-};
 
 void Check(bool cond, const char* what) {
     if (!cond) throw LogicError(Cat("LocalGemm: ", what));
@@ -313,6 +233,45 @@ Int EffectivePanel(const Grid& g, Int K, DType t) {
     return std::max<Int>(1, kc);
 }
 
+}  // namespace
+
+namespace detail {
+void FenceStreams(hipStream_t from, hipStream_t to) {
+    if (!from || !to || from == to) return;
+    hipEvent_t ev;
+    ELX_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    ELX_CHECK_HIP(hipEventRecord(ev, from));
+    ELX_CHECK_HIP(hipStreamWaitEvent(to, ev, 0));
+    ELX_CHECK_HIP(hipEventDestroy(ev));
+}
+
+std::shared_ptr<const DistMatrix> ReadProxy(const DistMatrix& A, const DistMatrix& tgt, Dist cd, Dist rd,
+                                            int calign, int ralign) {
+    const bool ok = A.Dev() == tgt.Dev() && A.ColDist() == cd && A.RowDist() == rd &&
+                    (calign < 0 || A.ColAlign() == calign) && (ralign < 0 || A.RowAlign() == ralign);
+    if (ok) {
+        if (A.Dev() != Device::GPU || A.Stream() == tgt.Stream())
+            return std::shared_ptr<const DistMatrix>(&A, [](const DistMatrix*) {});
+        auto V = DistMatrix::View(A, 0, A.Height(), 0, A.Width());
+        V->SetStream(tgt.Stream());
+        return V;
+    }
+    auto T = A.LikeOn(cd, rd, tgt.Dev());
+    T->SetStream(tgt.Stream());
+    // A's local block already holds exactly the (cd,rd) block on every rank
+    // (e.g. [MC,MR] -> [VC,*] on a 1x1 grid): relabel it in place, no copy
+    const int ca = calign >= 0 ? calign : 0, ra = ralign >= 0 ? ralign : 0;
+    if (A.Dev() == tgt.Dev() && A.Root() == 0 && SameLocalLayout(A, cd, rd, ca, ra)) {
+        T->Attach(A.Height(), A.Width(), ca, ra, const_cast<void*>(A.Buffer()), A.LDim(), 0);
+        if (A.Dev() == Device::GPU) FenceStreams(A.Stream(), tgt.Stream());
+        return T;
+    }
+    if (calign >= 0) T->AlignCols(calign, true);
+    if (ralign >= 0) T->AlignRows(ralign, true);
+    Copy(A, *T);
+    return T;
+}
+
 // ---------------------------------------------------------------------------
 // LocalTrrk (Trrk/Local.hpp:124-300): C_loc += alpha op(a) op(b) on the part of
 // C's local block whose GLOBAL index lies in the lower (gi >= gj) or upper
@@ -423,7 +382,7 @@ void TrrkLocal(bool lower, bool ta, bool tb, Int k, double alpha, const void* a,
 // uplo >= 0 (Syrk/Herk, Syrk/{LN,LT,UN,UT}.hpp): only C's lower (ELX_LOWER) or
 // upper (ELX_UPPER) triangle is updated, through TrrkLocal.
 void SummaC(int oA, int oB, double alpha, const DistMatrix& APre, const DistMatrix& BPre, double beta,
-            DistMatrix& CPre, int uplo = -1) {
+            DistMatrix& CPre, int uplo) {
     ELX_TRACE(uplo >= 0 ? "El::Trrk SUMMA_C" : "El::Gemm SUMMA_C");
     MultiSync sync(CPre.Stream(), {APre.Stream(), BPre.Stream()});
     auto Ap = ReadProxy(APre, CPre, Dist::MC, Dist::MR);
@@ -595,7 +554,9 @@ void SummaC(int oA, int oB, double alpha, const DistMatrix& APre, const DistMatr
     }
     Cp.Finish();
 }
+}  // namespace detail
 
+namespace {
 // ---------------------------------------------------------------------------
 // C-stationary multistream (NN_Multistream.hpp:262-412, NT/TN siblings): panel
 // p is gathered and applied by team p mod S, each on its own stream with its own
@@ -1011,544 +972,6 @@ void LocalGemmResize(int oA, int oB, double alpha, const DistMatrix& A, const Di
     }
     C.Resize(m, n);
     LocalGemm(oA, oB, alpha, A, B, 0.0, C);
-}
-
-void ScaleTrapezoid(double alpha, int uplo, DistMatrix& A, Int offset) {
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "ScaleTrapezoid: bad UpperOrLower ", uplo);
-    if (alpha == 1.0) return;  // ScaleTrapezoid.hpp:52-53
-    exec::Trapezoid(A.Dev(), A.Type(), uplo == ELX_LOWER, A.LocalHeight(), A.LocalWidth(), 0.0, nullptr, 0, alpha,
-                    A.Buffer(), A.LDim(), A.ColShift(), A.ColStride(), A.RowShift(), A.RowStride(), offset,
-                    A.Stream());
-}
-
-// Syrk / Herk on DistMatrices (src/blas_like/level3/Syrk.cpp:196-211): the
-// trapezoid of C is scaled by beta, then LN/LT/UN/UT run as the C-stationary
-// pipeline with the triangular local update (Syrk/LN.hpp:13-48 and siblings:
-// A1[MC,*] and A1^T[*,MR] per panel, LocalTrrk).  Real types only, so the
-// conjugate flag (Herk) changes nothing.  The reference switches to its Dot
-// variant when width > 10 height (LN.hpp:156); here the panel pipeline serves
-// every shape (same sums, summation order within the normwise tolerance).
-void Syrk(int uplo, int orient, double alpha, const DistMatrix& A, double beta, DistMatrix& C) {
-    ELX_TRACE("El::Syrk");
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Syrk: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "Syrk: bad orientation");
-    ELX_REQUIRE(&A.G() == &C.G(), "Syrk: matrices on different grids");
-    ELX_REQUIRE(A.Type() == C.Type(), "Syrk: mixed types");
-    const bool N = orient == ELX_NORMAL;
-    const Int n = N ? A.Height() : A.Width();
-    if (C.Height() != n || C.Width() != n) throw LogicError("Nonconformal Syrk");
-    ScaleTrapezoid(beta, uplo, C, 0);
-    if (N) SummaC(ELX_NORMAL, ELX_TRANSPOSE, alpha, A, A, 1.0, C, uplo);
-    else SummaC(ELX_TRANSPOSE, ELX_NORMAL, alpha, A, A, 1.0, C, uplo);
-}
-
-// Trrk on DistMatrices (src/blas_like/level3/Trrk.cpp:100-117): C := alpha op(A)
-// op(B) + beta C on C's uplo triangle; TrrkNN/NT/TN/TT are the same C-stationary
-// pipeline with the triangular local update.
-void Trrk(int uplo, int oA, int oB, double alpha, const DistMatrix& A, const DistMatrix& B, double beta,
-          DistMatrix& C) {
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trrk: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(&A.G() == &B.G() && &A.G() == &C.G(), "Trrk: matrices on different grids");
-    ELX_REQUIRE(A.Type() == B.Type() && A.Type() == C.Type(), "Trrk: mixed types");
-    if (oA == ELX_ADJOINT) oA = ELX_TRANSPOSE;
-    if (oB == ELX_ADJOINT) oB = ELX_TRANSPOSE;
-    const Int m = IsN(oA) ? A.Height() : A.Width(), k = IsN(oA) ? A.Width() : A.Height();
-    const Int kb = IsN(oB) ? B.Height() : B.Width(), n = IsN(oB) ? B.Width() : B.Height();
-    if (m != C.Height() || n != C.Width() || k != kb || m != n) throw LogicError("Nonconformal Trrk");
-    ScaleTrapezoid(beta, uplo, C, 0);
-    SummaC(oA, oB, alpha, A, B, 1.0, C, uplo);
-}
-
-// Syr2k / Her2k (src/blas_like/level3/Syr2k.cpp:78-93, Syr2k/LN.hpp): C := alpha
-// (op(A) op(B)^T + op(B) op(A)^T) + beta C on C's uplo triangle.  The reference
-// gathers both panels and runs two LocalTrrks per panel; here each term is one
-// pass of the triangular pipeline.  Real types: conj(alpha) = alpha.
-void Syr2k(int uplo, int orient, double alpha, const DistMatrix& A, const DistMatrix& B, double beta,
-           DistMatrix& C) {
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Syr2k: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "Syr2k: bad orientation");
-    ELX_REQUIRE(&A.G() == &B.G() && &A.G() == &C.G(), "Syr2k: matrices on different grids");
-    ELX_REQUIRE(A.Type() == B.Type() && A.Type() == C.Type(), "Syr2k: mixed types");
-    const bool N = orient == ELX_NORMAL;
-    const Int n = N ? A.Height() : A.Width();
-    if (A.Height() != B.Height() || A.Width() != B.Width() || C.Height() != n || C.Width() != n)
-        throw LogicError("Nonconformal Syr2k");
-    ScaleTrapezoid(beta, uplo, C, 0);
-    const int oA = N ? ELX_NORMAL : ELX_TRANSPOSE, oB = N ? ELX_TRANSPOSE : ELX_NORMAL;
-    SummaC(oA, oB, alpha, A, B, 1.0, C, uplo);
-    SummaC(oA, oB, alpha, B, A, 1.0, C, uplo);
-}
-
-// Trsm on DistMatrices (src/blas_like/level3/Trsm.cpp:129-420): B := alpha
-// op(A)^-1 B (LEFT) or alpha B op(A)^-1 (RIGHT).  LEFT follows Trsm/LLN.hpp:40-70
-// (and LUN/LLT/LUT with the block order reversed where op(A) is upper):
-//   A11[*,*] <- A11;  X1[*,VR] <- X1;  X1[*,VR] := op(A11)^-1 X1 (trsm_kernel);
-//   X1 <- X1[*,VR];   X_rest -= op(A)_rest,1 X1 (the C-stationary SUMMA on views:
-//   op(A) panel gathered [MC,*] / [*,MC], X1 as [*,MR], MFMA update).
-// RIGHT solves the transposed LEFT problem (X op(A) = B <=> op(A)^T X^T = B^T)
-// through two distributed transposes.  f64/f32 (the reference's GPU Trsm types).
-// ELX_TRSM_FLAT=1: the reference's flat nb-step sweep (every update k = nb over
-// all remaining rows) instead of the recursive split (tests, ablation)
-bool TrsmFlat() {
-    static const bool v = [] { const char* e = getenv("ELX_TRSM_FLAT"); return e && atoi(e) > 0; }();
-    return v;
-}
-
-void TrsmLeft(int uplo, int orient, bool unit, const DistMatrix& APre, DistMatrix& XPre) {
-    ELX_TRACE("El::Trsm");
-    MultiSync sync(XPre.Stream(), {APre.Stream()});
-    auto Ap = ReadProxy(APre, XPre, Dist::MC, Dist::MR);
-    const DistMatrix& A = *Ap;
-    RWProxy Xp(XPre);
-    DistMatrix& X = Xp.Get();
-    const Int m = X.Height(), n = X.Width();
-    Int nb = std::max<Int>(1, Blocksize());
-    const bool trans = orient != ELX_NORMAL, lower = uplo == ELX_LOWER;
-    const bool forward = lower != trans;  // op(A) lower: blocks top to bottom
-    auto A11s = A.Like(Dist::STAR, Dist::STAR);
-    auto X1v = X.Like(Dist::STAR, Dist::VR);
-    // X_rest -= op(A)(r0:r1, k0:k1) X(k0:k1, :) through the SUMMA pipeline on views
-    // (solved rows are read from `src`: X itself, or Y on the batched path)
-    const DistMatrix* src = &X;
-    bool local = false;  // set on the batched path: every operand's local block is the whole matrix
-    auto update = [&](Int r0, Int r1, Int k0, Int k1) {
-        if (r1 <= r0 || k1 <= k0 || n == 0) return;
-        if (local) {  // one MFMA GEMM on the local blocks: no views, proxies or pipeline on the host
-            const size_t es = DTypeSize(X.Type());
-            const char* a = static_cast<const char*>(A.Buffer()) +
-                            ((trans ? k0 + r0 * A.LDim() : r0 + k0 * A.LDim()) * es);
-            const char* y = static_cast<const char*>(src->Buffer()) + k0 * es;
-            char* x = static_cast<char*>(X.Buffer()) + r0 * es;
-            exec::Gemm(X.Dev(), X.Type(), trans, false, r1 - r0, n, k1 - k0, -1.0, a, A.LDim(), y, src->LDim(), 1.0, x,
-                       X.LDim(), X.Stream());
-            return;
-        }
-        auto Ar = trans ? DistMatrix::View(A, k0, k1, r0, r1) : DistMatrix::View(A, r0, r1, k0, k1);
-        auto Xk = DistMatrix::View(*src, k0, k1, 0, n);
-        auto Xr = DistMatrix::View(X, r0, r1, 0, n);
-        SummaC(trans ? ELX_TRANSPOSE : ELX_NORMAL, ELX_NORMAL, -1.0, *Ar, *Xk, 1.0, *Xr);
-    };
-    // A whose local block is the whole matrix (1x1 grid): every diagonal block's
-    // inverse comes from ONE batched launch up front (the per-block inversions
-    // are independent), applied per block as an MFMA GEMM whose output goes
-    // straight into a second buffer Y (no write-back per block; every later
-    // update reads solved rows from Y, copied into X once at the end);
-    // elsewhere each block is solved where it lands (exec::Trsm)
-    const size_t es = DTypeSize(X.Type());
-    Buffer winv;
-    auto batch_ok = [&](Int b) {
-        return X.Dev() == Device::GPU && SameLocalLayout(A, Dist::STAR, Dist::STAR, 0, 0) &&
-               b * 65 * (Int)es <= kern::kTriInverseLdsMax && (m + b - 1) / b <= 65535 &&
-               kern::tri_inverse_lds_ok(static_cast<int>(X.Type()), b) &&
-               SameLocalLayout(X, Dist::STAR, Dist::VR, 0, X.RowAlign()) && X.LocalWidth() >= 4 * b;
-    };
-    // Batched path with the default Blocksize (128) and a large system: 256-row
-    // diagonal blocks, so every leaf (inverse applied as a GEMM) and the lowest
-    // updates are 256 x n MFMA launches (256 output tiles, the whole machine)
-    // instead of 128 x n ones (half of it); ELX_TRSM_NB256=0 keeps 128.
-    static const bool nb256 = [] { const char* e = getenv("ELX_TRSM_NB256"); return !e || atoi(e) != 0; }();
-    if (nb256 && nb == 128 && m >= 8 * 256 && batch_ok(256)) nb = 256;
-    const bool batched = batch_ok(nb);
-    std::shared_ptr<DistMatrix> Y;
-    if (batched) {
-        FenceStreams(A.Stream(), X.Stream());
-        winv.Reset(Device::GPU, static_cast<size_t>((m + nb - 1) / nb) * nb * nb * es, X.Stream());
-        exec::TriInverseBatched(X.Type(), lower, trans, unit, nb, m, A.Buffer(), A.LDim(), winv.data(), X.Stream());
-        Y = X.Like(Dist::MC, Dist::MR);
-        Y->Align(X.ColAlign(), X.RowAlign(), true);
-        Y->Resize(m, n);
-        src = Y.get();
-        local = X.LocalHeight() == m && X.LocalWidth() == n && Y->LDim() > 0 && !getenv("ELX_TRSM_SUMMA");
-    }
-    // X(k0:k1, :) := op(A11)^-1 X(k0:k1, :), one nb block (Trsm/LLN.hpp:49-60)
-    auto leaf = [&](Int k0, Int k1) {
-        auto X1 = DistMatrix::View(X, k0, k1, 0, n);
-        if (batched) {
-            auto Y1 = DistMatrix::View(*Y, k0, k1, 0, n);
-            exec::Gemm(X.Dev(), X.Type(), false, false, k1 - k0, X1->LocalWidth(), k1 - k0, 1.0,
-                       static_cast<const char*>(winv.data()) + (k0 / nb) * nb * nb * es, nb, X1->Buffer(),
-                       X1->LDim(), 0.0, Y1->Buffer(), Y1->LDim(), X1->Stream());
-            return;
-        }
-        // a block whose local storage already IS the [*,*] / [*,VR] layout (a
-        // 1x1 grid) is used in place: no redistribution temporaries
-        auto A11 = DistMatrix::View(A, k0, k1, k0, k1);
-        std::shared_ptr<const DistMatrix> a11 = A11;
-        if (!SameLocalLayout(*A11, Dist::STAR, Dist::STAR, 0, 0)) {
-            Copy(*A11, *A11s);                               // A11[*,*] <- A11[MC,MR]
-            a11 = A11s;
-        }
-        const bool inplace = SameLocalLayout(*X1, Dist::STAR, Dist::VR, 0, X1->RowAlign());
-        DistMatrix* x1 = X1.get();
-        if (!inplace) {
-            X1v->AlignRows(X.RowAlign(), true);
-            Copy(*X1, *X1v);                                 // X1[*,VR] <- X1[MC,MR]
-            x1 = X1v.get();
-        }
-        if (X.Dev() == Device::GPU) FenceStreams(a11->Stream(), x1->Stream());
-        exec::Trsm(X.Dev(), X.Type(), lower, trans, unit, k1 - k0, x1->LocalWidth(), a11->Buffer(), a11->LDim(),
-                   x1->Buffer(), x1->LDim(), x1->Stream());
-        if (!inplace) Copy(*X1v, *X1);                       // X1[MC,MR] <- X1[*,VR]
-    };
-    const Int nblk = (m + nb - 1) / nb;
-    if (TrsmFlat()) {
-        // the reference's order (Trsm/LLN.hpp:40-70): solve block b, then update
-        // every remaining row with k = nb
-        for (Int bi = 0; bi < nblk; ++bi) {
-            const Int b = forward ? bi : nblk - 1 - bi;
-            const Int k0 = b * nb, k1 = std::min(m, k0 + nb);
-            leaf(k0, k1);
-            if (forward) update(k1, m, k0, k1);
-            else update(0, k0, k0, k1);
-        }
-    } else {
-        // Recursive split at a block boundary: solve the half op(A) reaches first,
-        // eliminate it from the other half with ONE GEMM (k = that half's height),
-        // solve the other half.  The same eliminations as the nb-step sweep, but
-        // half of all update FLOPs go to a k = m/2 GEMM, a quarter to two k = m/4
-        // ones, ...: deep, full-machine MFMA launches instead of m/nb k = nb ones.
-        std::function<void(Int, Int)> solve = [&](Int K0, Int K1) {
-            const Int nbk = (K1 - K0 + nb - 1) / nb;
-            if (nbk <= 1) return leaf(K0, K1);
-            const Int mid = K0 + (nbk / 2) * nb;
-            if (forward) {
-                solve(K0, mid);
-                update(mid, K1, K0, mid);
-                solve(mid, K1);
-            } else {
-                solve(mid, K1);
-                update(K0, mid, mid, K1);
-                solve(K0, mid);
-            }
-        };
-        if (m > 0) solve(0, m);
-    }
-    if (Y) Copy(*Y, X);
-    Xp.Finish();
-}
-
-void Trsm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B,
-          bool checkIfSingular) {
-    ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Trsm: bad LeftOrRight ", side);
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trsm: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "Trsm: bad orientation");
-    ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "Trsm: bad UnitOrNonUnit ", diag);
-    ELX_REQUIRE(&A.G() == &B.G(), "Trsm: matrices on different grids");
-    ELX_REQUIRE(A.Type() == B.Type(), "Trsm: mixed types");
-    if (A.Type() != DType::F64 && A.Type() != DType::F32) throw LogicError("Trsm: only float and double are supported");
-    if (A.Height() != A.Width()) throw LogicError("A must be square");  // Trsm.cpp:142-143
-    if ((side == ELX_LEFT ? B.Height() : B.Width()) != A.Height()) throw LogicError("Nonconformal Trsm");
-    if (checkIfSingular && diag != ELX_UNIT && DiagonalHasZero(A)) throw SingularMatrixError();
-    Scale(alpha, B);  // Trsm.cpp:155 (B *= alpha)
-    if (side == ELX_LEFT) return TrsmLeft(uplo, orient, diag == ELX_UNIT, A, B);
-    auto Bt = B.Like(Dist::MC, Dist::MR);
-    Transpose(B, *Bt);
-    TrsmLeft(uplo, orient == ELX_NORMAL ? ELX_TRANSPOSE : ELX_NORMAL, diag == ELX_UNIT, A, *Bt);
-    Transpose(*Bt, B);
-}
-
-// Cholesky on a DistMatrix (src/lapack_like/factor/Cholesky/LowerVariant3.hpp:
-// 78-134 and UpperVariant3.hpp): A = L L^T (LOWER) or U^T U (UPPER) in place on
-// the uplo triangle; the other triangle is neither read nor written.  The
-// reference sweeps nb columns at a time (factor A11, solve the panel under it,
-// update all of A22 with k = nb).  Here the same three steps are split
-// recursively at block boundaries, as TrsmLeft is:
-//   factor A11 (recursion);  A21 := A21 L11^-T (Trsm);  A22 -= A21 A21^T (Syrk);
-//   factor A22 (recursion)
-// so half of the update FLOPs run as one k = n/2 Syrk, a quarter as two k = n/4
-// ones, ...  A leaf is one diagonal block of at most min(Blocksize(),
-// kPotrfMax) rows: A11[*,*] <- A11, factored redundantly on every rank
-// (potrf_kernel on the GPU), A11 <- A11[*,*]; in place where the local storage
-// already is the [*,*] layout (1x1 grid).  One info word lives for the whole
-// call: a leaf whose pivot is not > 0 records the 1-based column, later leaves
-// see it and do nothing, and it is read back once after the last leaf; every
-// rank factors the same leaves, so all ranks throw NonHPDMatrixError together.
-// ELX_CHOLESKY_FLAT=1: the reference's flat nb-step order (ablation).  f64/f32.
-void Cholesky(int uplo, DistMatrix& APre) {
-    ELX_TRACE("El::Cholesky");
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Cholesky: bad UpperOrLower ", uplo);
-    if (APre.Height() != APre.Width()) throw LogicError("A must be square");
-    if (APre.Type() != DType::F64 && APre.Type() != DType::F32)
-        throw LogicError("Cholesky: only float and double are supported");
-    RWProxy Ap(APre);
-    DistMatrix& A = Ap.Get();
-    const Int n = A.Height();
-    const bool lower = uplo == ELX_LOWER, gpu = A.Dev() == Device::GPU;
-    const Int nb = std::max<Int>(1, std::min<Int>(Blocksize(), kern::kPotrfMax));
-    int info_host = 0;
-    int* info = &info_host;
-    Buffer info_dev;
-    if (gpu) {
-        info_dev.Reset(Device::GPU, sizeof(int), A.Stream());
-        info = static_cast<int*>(info_dev.data());
-        ELX_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(int), A.Stream()));
-    }
-    auto A11s = A.Like(Dist::STAR, Dist::STAR);
-    auto leaf = [&](Int k0, Int k1) {
-        auto A11 = DistMatrix::View(A, k0, k1, k0, k1);
-        DistMatrix* a11 = A11.get();
-        const bool inplace = SameLocalLayout(*A11, Dist::STAR, Dist::STAR, 0, 0);
-        if (!inplace) {
-            Copy(*A11, *A11s);                               // A11[*,*] <- A11[MC,MR]
-            a11 = A11s.get();
-        }
-        exec::Cholesky(A.Dev(), A.Type(), lower, k1 - k0, a11->Buffer(), std::max<Int>(1, a11->LDim()), info,
-                       static_cast<int>(k0), a11->Stream());
-        if (!inplace) Copy(*A11s, *A11);                     // A11[MC,MR] <- A11[*,*]
-    };
-    // the panel beside A(k0:mid, k0:mid) and the trailing block A(mid:k1, mid:k1)
-    auto eliminate = [&](Int k0, Int mid, Int k1) {
-        auto A11 = DistMatrix::View(A, k0, mid, k0, mid);
-        auto A22 = DistMatrix::View(A, mid, k1, mid, k1);
-        if (lower) {
-            auto A21 = DistMatrix::View(A, mid, k1, k0, mid);
-            Trsm(ELX_RIGHT, ELX_LOWER, ELX_TRANSPOSE, ELX_NON_UNIT, 1.0, *A11, *A21);
-            Syrk(ELX_LOWER, ELX_NORMAL, -1.0, *A21, 1.0, *A22);
-        } else {
-            auto A12 = DistMatrix::View(A, k0, mid, mid, k1);
-            Trsm(ELX_LEFT, ELX_UPPER, ELX_TRANSPOSE, ELX_NON_UNIT, 1.0, *A11, *A12);
-            Syrk(ELX_UPPER, ELX_TRANSPOSE, -1.0, *A12, 1.0, *A22);
-        }
-    };
-    // A whose local block is the whole matrix on the GPU (1x1 grid): the recursion
-    // stops at blocks of ELX_CHOLESKY_SWEEP rows (default 1024; 0: recurse down to
-    // single leaves; read per call, for A/B) and sweeps such a block leaf by leaf
-    // with direct launches on the local buffer: potrf leaf, op(A11)^-T from the
-    // batched inverse kernel, the panel as one MFMA GEMM with it, the trailing
-    // triangle through TrrkLocal.  The same eliminations, but six launches per
-    // leaf instead of a Trsm and a Syrk call on views (proxies, transposes and
-    // pipeline set-up: ~0.4 ms of host time per leaf, which made the run time
-    // linear in n: profiles/cholesky_bench.log).
-    const char* sweep_s = getenv("ELX_CHOLESKY_SWEEP");
-    const bool local = gpu && SameLocalLayout(A, Dist::STAR, Dist::STAR, 0, 0) && A.LocalHeight() == n &&
-                       A.LocalWidth() == n && A.LDim() > 0 &&
-                       kern::tri_inverse_lds_ok(static_cast<int>(A.Type()), nb);
-    const Int sweep_rows = local ? (sweep_s ? (Int)atoll(sweep_s) : (Int)1024) : 0;
-    Buffer winv, ybuf, ttmp;
-    auto sweep = [&](Int K0, Int K1) {
-        const DType t = A.Type();
-        const size_t es = DTypeSize(t);
-        const Int ld = A.LDim();
-        hipStream_t s = A.Stream();
-        auto at = [&](Int i, Int j) { return static_cast<char*>(A.Buffer()) + (i + j * ld) * es; };
-        for (Int k0 = K0; k0 < K1; k0 += nb) {
-            const Int k1 = std::min(K1, k0 + nb), kb = k1 - k0, rest = K1 - k1;
-            exec::Cholesky(Device::GPU, t, lower, kb, at(k0, k0), ld, info, static_cast<int>(k0), s);
-            if (rest == 0) break;
-            if (winv.bytes() < static_cast<size_t>(kb * kb) * es) winv.Reset(Device::GPU, nb * nb * es, s);
-            if (ybuf.bytes() < static_cast<size_t>(rest * kb) * es) ybuf.Reset(Device::GPU, (K1 - K0) * nb * es, s);
-            // W := op(A11)^-1 with op = transpose: L11^-T (lower) / U11^-T (upper)
-            exec::TriInverseBatched(t, lower, true, false, kb, kb, at(k0, k0), ld, winv.data(), s);
-            char* panel = lower ? at(k1, k0) : at(k0, k1);
-            if (lower) {  // A21 := A21 L11^-T
-                exec::Gemm(Device::GPU, t, false, false, rest, kb, kb, 1.0, panel, ld, winv.data(), kb, 0.0, ybuf.data(),
-                           rest, s);
-                const kern::Copy2D back{rest, kb, ybuf.data(), 1, rest, panel, 1, ld};
-                exec::Copy2DBatch(Device::GPU, t, &back, 1, false, 0.0, s);
-            } else {      // A12 := U11^-T A12
-                exec::Gemm(Device::GPU, t, false, false, kb, rest, kb, 1.0, winv.data(), kb, panel, ld, 0.0, ybuf.data(),
-                           kb, s);
-                const kern::Copy2D back{kb, rest, ybuf.data(), 1, kb, panel, 1, ld};
-                exec::Copy2DBatch(Device::GPU, t, &back, 1, false, 0.0, s);
-            }
-            // A22 -= A21 A21^T (lower) / A12^T A12 (upper), on A22's uplo triangle only
-            auto A22 = DistMatrix::View(A, k1, K1, k1, K1);
-            TrrkLocal(lower, !lower, lower, kb, -1.0, panel, ld, panel, ld, *A22, s, ttmp);
-        }
-    };
-    const char* flat_s = getenv("ELX_CHOLESKY_FLAT");  // read per call, for A/B
-    const bool flat = flat_s && atoi(flat_s) > 0;
-    if (flat) {
-        for (Int k0 = 0; k0 < n; k0 += nb) {
-            const Int k1 = std::min(n, k0 + nb);
-            leaf(k0, k1);
-            if (k1 < n) eliminate(k0, k1, n);
-        }
-    } else {
-        std::function<void(Int, Int)> factor = [&](Int K0, Int K1) {
-            const Int nbk = (K1 - K0 + nb - 1) / nb;
-            if (nbk <= 1) return leaf(K0, K1);
-            if (K1 - K0 <= sweep_rows) return sweep(K0, K1);
-            const Int mid = K0 + (nbk / 2) * nb;
-            factor(K0, mid);
-            eliminate(K0, mid, K1);
-            factor(mid, K1);
-        };
-        if (n > 0) factor(0, n);
-    }
-    int column = info_host;
-    if (gpu && n > 0) {
-        ELX_CHECK_HIP(hipMemcpyAsync(&column, info, sizeof(int), hipMemcpyDeviceToHost, A.Stream()));
-        ELX_CHECK_HIP(hipStreamSynchronize(A.Stream()));
-    }
-    if (column != 0) throw NonHPDMatrixError(column);
-    Ap.Finish();
-}
-
-// cholesky::SolveAfter (src/lapack_like/factor/Cholesky/SolveAfter.hpp:78-107):
-// B := A^-1 B from the factor A holds in its uplo triangle.  Real types: the
-// orientation changes nothing (A is symmetric; the reference only conjugates B).
-namespace cholesky {
-void SolveAfter(int uplo, int orient, const DistMatrix& A, DistMatrix& B) {
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "SolveAfter: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "SolveAfter: bad orientation");
-    if (A.Height() != A.Width()) throw LogicError("A must be square");
-    if (A.Height() != B.Height()) throw LogicError("A and B must be the same height");
-    if (uplo == ELX_LOWER) {
-        Trsm(ELX_LEFT, ELX_LOWER, ELX_NORMAL, ELX_NON_UNIT, 1.0, A, B);
-        Trsm(ELX_LEFT, ELX_LOWER, ELX_TRANSPOSE, ELX_NON_UNIT, 1.0, A, B);
-    } else {
-        Trsm(ELX_LEFT, ELX_UPPER, ELX_TRANSPOSE, ELX_NON_UNIT, 1.0, A, B);
-        Trsm(ELX_LEFT, ELX_UPPER, ELX_NORMAL, ELX_NON_UNIT, 1.0, A, B);
-    }
-}
-}  // namespace cholesky
-
-// Trmm on DistMatrices (src/blas_like/level3/Trmm.cpp:53-89): B := alpha
-// op(tri(A)) B (LEFT) or alpha B op(tri(A)) (RIGHT), in place.  LEFT is the
-// reference's LLNC / LUNC sweep (Trmm/LLN.hpp:178-228) in the order that never
-// overwrites rows still to be read, split recursively at block boundaries as
-// TrsmLeft is: with op(A) lower,
-//   X[mid:K1] := op(A)[mid:K1, mid:K1] X[mid:K1]       (recursion)
-//   X[mid:K1] += op(A)[mid:K1, K0:mid] X[K0:mid]       (C-stationary SUMMA on views)
-//   X[K0:mid] := op(A)[K0:mid, K0:mid] X[K0:mid]       (recursion)
-// and mirrored with op(A) upper.  A leaf is one diagonal block: A11[*,*] <- A11,
-// X1[*,VR] <- X1, X1 := op(tri(A11)) X1 (trmm_tile_kernel, which skips the zero
-// half of A11), X1 <- X1[*,VR].  RIGHT runs the transposed LEFT problem through
-// two distributed transposes, as Trsm does.  f64/f32.
-void TrmmLeft(int uplo, int orient, bool unit, const DistMatrix& APre, DistMatrix& XPre) {
-    ELX_TRACE("El::Trmm");
-    MultiSync sync(XPre.Stream(), {APre.Stream()});
-    auto Ap = ReadProxy(APre, XPre, Dist::MC, Dist::MR);
-    const DistMatrix& A = *Ap;
-    RWProxy Xp(XPre);
-    DistMatrix& X = Xp.Get();
-    const Int m = X.Height(), n = X.Width();
-    Int nb = std::max<Int>(1, Blocksize());
-    const bool trans = orient != ELX_NORMAL, lower = uplo == ELX_LOWER;
-    const bool op_lower = lower != trans;
-    auto A11s = A.Like(Dist::STAR, Dist::STAR);
-    auto X1v = X.Like(Dist::STAR, Dist::VR);
-    // every operand's local block is the whole matrix (1x1 grid): updates are
-    // direct MFMA GEMMs on the local buffers, no views, proxies or pipeline
-    const bool local = SameLocalLayout(A, Dist::STAR, Dist::STAR, 0, 0) &&
-                       SameLocalLayout(X, Dist::STAR, Dist::VR, 0, X.RowAlign()) && X.LocalHeight() == m &&
-                       X.LocalWidth() == n && X.LDim() > 0;
-    // There, with the default Blocksize (128) on the GPU, the leaf is widened to
-    // ELX_TRMM_LEAF rows (default 512; 0 keeps the blocksize) once the matrix
-    // holds two of them: one triangle-aware launch that fills the chip instead
-    // of a cascade of 128-row leaves and k = 128, 256, ... updates (read per
-    // call, for A/B)
-    const char* leaf_s = getenv("ELX_TRMM_LEAF");
-    const Int leaf_env = leaf_s ? (Int)atoll(leaf_s) : (Int)512;
-    if (local && X.Dev() == Device::GPU && nb == 128 && leaf_env > nb && m >= 2 * leaf_env) nb = leaf_env;
-    if (local && X.Dev() == Device::GPU) FenceStreams(A.Stream(), X.Stream());
-    // X(r0:r1, :) += op(A)(r0:r1, k0:k1) X(k0:k1, :)
-    auto update = [&](Int r0, Int r1, Int k0, Int k1) {
-        if (r1 <= r0 || k1 <= k0 || n == 0) return;
-        if (local) {
-            const size_t es = DTypeSize(X.Type());
-            const char* a = static_cast<const char*>(A.Buffer()) +
-                            ((trans ? k0 + r0 * A.LDim() : r0 + k0 * A.LDim()) * es);
-            const char* xk = static_cast<const char*>(X.Buffer()) + k0 * es;
-            char* xr = static_cast<char*>(X.Buffer()) + r0 * es;
-            exec::Gemm(X.Dev(), X.Type(), trans, false, r1 - r0, n, k1 - k0, 1.0, a, A.LDim(), xk, X.LDim(), 1.0, xr,
-                       X.LDim(), X.Stream());
-            return;
-        }
-        auto Ar = trans ? DistMatrix::View(A, k0, k1, r0, r1) : DistMatrix::View(A, r0, r1, k0, k1);
-        auto Xk = DistMatrix::View(X, k0, k1, 0, n);
-        auto Xr = DistMatrix::View(X, r0, r1, 0, n);
-        SummaC(trans ? ELX_TRANSPOSE : ELX_NORMAL, ELX_NORMAL, 1.0, *Ar, *Xk, 1.0, *Xr);
-    };
-    // X(k0:k1, :) := op(tri(A11)) X(k0:k1, :), one diagonal block
-    auto leaf = [&](Int k0, Int k1) {
-        auto X1 = DistMatrix::View(X, k0, k1, 0, n);
-        // a block whose local storage already IS the [*,*] / [*,VR] layout (a
-        // 1x1 grid) is used in place: no redistribution temporaries
-        auto A11 = DistMatrix::View(A, k0, k1, k0, k1);
-        std::shared_ptr<const DistMatrix> a11 = A11;
-        if (!SameLocalLayout(*A11, Dist::STAR, Dist::STAR, 0, 0)) {
-            Copy(*A11, *A11s);                               // A11[*,*] <- A11[MC,MR]
-            a11 = A11s;
-        }
-        const bool inplace = SameLocalLayout(*X1, Dist::STAR, Dist::VR, 0, X1->RowAlign());
-        DistMatrix* x1 = X1.get();
-        if (!inplace) {
-            X1v->AlignRows(X.RowAlign(), true);
-            Copy(*X1, *X1v);                                 // X1[*,VR] <- X1[MC,MR]
-            x1 = X1v.get();
-        }
-        if (X.Dev() == Device::GPU) FenceStreams(a11->Stream(), x1->Stream());
-        exec::Trmm(X.Dev(), X.Type(), lower, trans, unit, k1 - k0, x1->LocalWidth(), 1.0, a11->Buffer(), a11->LDim(),
-                   x1->Buffer(), x1->LDim(), x1->Stream());
-        if (!inplace) Copy(*X1v, *X1);                       // X1[MC,MR] <- X1[*,VR]
-    };
-    std::function<void(Int, Int)> mul = [&](Int K0, Int K1) {
-        const Int nbk = (K1 - K0 + nb - 1) / nb;
-        if (nbk <= 1) return leaf(K0, K1);
-        const Int mid = K0 + (nbk / 2) * nb;
-        if (op_lower) {
-            mul(mid, K1);
-            update(mid, K1, K0, mid);
-            mul(K0, mid);
-        } else {
-            mul(K0, mid);
-            update(K0, mid, mid, K1);
-            mul(mid, K1);
-        }
-    };
-    if (m > 0 && n > 0) mul(0, m);
-    Xp.Finish();
-}
-
-void Trmm(int side, int uplo, int orient, int diag, double alpha, const DistMatrix& A, DistMatrix& B) {
-    ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Trmm: bad LeftOrRight ", side);
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trmm: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "Trmm: bad orientation");
-    ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "Trmm: bad UnitOrNonUnit ", diag);
-    ELX_REQUIRE(&A.G() == &B.G(), "Trmm: matrices on different grids");
-    ELX_REQUIRE(A.Type() == B.Type(), "Trmm: mixed types");
-    if (A.Type() != DType::F64 && A.Type() != DType::F32) throw LogicError("Trmm: only float and double are supported");
-    if (A.Height() != A.Width()) throw LogicError("Triangular matrix must be square");  // Trmm.cpp:31-32
-    if ((side == ELX_LEFT ? B.Height() : B.Width()) != A.Height()) throw LogicError("Nonconformal Trmm");
-    Scale(alpha, B);  // Trmm.cpp:60 (X *= alpha)
-    if (side == ELX_LEFT) return TrmmLeft(uplo, orient, diag == ELX_UNIT, A, B);
-    // B op(A) = (op(A)^T B^T)^T
-    auto Bt = B.Like(Dist::MC, Dist::MR);
-    Transpose(B, *Bt);
-    TrmmLeft(uplo, orient == ELX_NORMAL ? ELX_TRANSPOSE : ELX_NORMAL, diag == ELX_UNIT, A, *Bt);
-    Transpose(*Bt, B);
-}
-
-// Symm / Hemm on DistMatrices (src/blas_like/level3/Symm.cpp:55-80): C := alpha
-// A B + beta C (LEFT) or alpha B A + beta C (RIGHT), A symmetric with only its
-// uplo triangle read.  The reference accumulates triangle-aware local products
-// (Symm/LL.hpp LocalAccumulateLL); here A is completed once into a full [MC,MR]
-// copy (one distributed transpose + a trapezoid copy of the mirrored strict
-// triangle, O(n^2) HBM work) and the product runs through El::Gemm's pipeline.
-void Symm(int side, int uplo, double alpha, const DistMatrix& A, const DistMatrix& B, double beta, DistMatrix& C) {
-    ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Symm: bad LeftOrRight ", side);
-    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Symm: bad UpperOrLower ", uplo);
-    ELX_REQUIRE(&A.G() == &B.G() && &A.G() == &C.G(), "Symm: matrices on different grids");
-    ELX_REQUIRE(A.Type() == B.Type() && A.Type() == C.Type(), "Symm: mixed types");
-    if (A.Height() != A.Width()) throw LogicError("A must be square");
-    const bool left = side == ELX_LEFT;
-    if ((left ? B.Height() : B.Width()) != A.Height() || C.Height() != B.Height() || C.Width() != B.Width())
-        throw LogicError("Nonconformal Symm");
-    auto S = A.Like(Dist::MC, Dist::MR);
-    Copy(A, *S);
-    auto T = A.Like(Dist::MC, Dist::MR);
-    T->AlignWith(*S, true);
-    Transpose(*S, *T);
-    // S's strictly-other triangle := T's (lower stored: strict upper is gi <= gj - 1)
-    const bool other_lower = uplo == ELX_UPPER;
-    if (S->Dev() == Device::GPU) FenceStreams(T->Stream(), S->Stream());
-    exec::Trapezoid(S->Dev(), S->Type(), other_lower, S->LocalHeight(), S->LocalWidth(), 1.0, T->Buffer(), T->LDim(),
-                    0.0, S->Buffer(), S->LDim(), S->ColShift(), S->ColStride(), S->RowShift(), S->RowStride(),
-                    other_lower ? -1 : 1, S->Stream());
-    if (left) Gemm(ELX_NORMAL, ELX_NORMAL, alpha, *S, B, beta, C, ELX_GEMM_DEFAULT);
-    else Gemm(ELX_NORMAL, ELX_NORMAL, alpha, B, *S, beta, C, ELX_GEMM_DEFAULT);
 }
 
 void Gemm(int oA, int oB, double alpha, const DistMatrix& A, const DistMatrix& B, double beta, DistMatrix& C,
