@@ -83,6 +83,9 @@ _SIGS = {
     "elx_matrix_copy": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_trmm": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_cholesky": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
+    "elx_matrix_triangular_inverse": (_i, [_i, _i, _i, _i, _i64, _vp, _i64, _vp]),
+    "elx_matrix_trtrmm": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
+    "elx_matrix_hpd_inverse": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -176,6 +179,9 @@ _SIGS = {
     "elx_cholesky": (_i, [_i, _vp]),
     "elx_cholesky_leaf_max": (_i64, []),
     "elx_cholesky_solve_after": (_i, [_i, _i, _vp, _vp]),
+    "elx_triangular_inverse": (_i, [_i, _i, _vp]),
+    "elx_trtrmm": (_i, [_i, _vp, _i]),
+    "elx_hpd_inverse": (_i, [_i, _vp]),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),

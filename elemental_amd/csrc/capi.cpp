@@ -9,6 +9,7 @@
 #include "core/random.hpp"
 #include "core/io.hpp"
 #include "core/exec.hpp"
+#include <functional>
 #include <string>
 
 struct elx_comm_s { std::shared_ptr<elx::Comm> c; };
@@ -287,6 +288,44 @@ int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int
         if (d == Device::GPU) M.SetStream(DevStream(d, stream));
         Cholesky(uplo, M);
     });
+}
+
+namespace {
+// The checks and the attachment elx_matrix_cholesky makes, for the three inverse
+// entry points: `run` gets the buffer as a 1x1-grid [MC,MR] matrix on the stream.
+int MatrixInverseOp(const char* who, int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream,
+                    const std::function<void(DistMatrix&)>& run) {
+    return Guard([&] {
+        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, who, ": bad UpperOrLower ", uplo);
+        ELX_REQUIRE(n >= 0, "negative ", who, " dimension");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+        CheckLd(lda, n, "A");
+        if (n == 0) return;
+        static const auto grid = std::make_shared<Grid>(Comm::Self(), 1, ELX_COLUMN_MAJOR);
+        DistMatrix M(grid, t, Dist::MC, Dist::MR, d);
+        M.Attach(n, n, 0, 0, A, lda, 0);
+        if (d == Device::GPU) M.SetStream(DevStream(d, stream));
+        run(M);
+    });
+}
+}  // namespace
+
+int elx_matrix_triangular_inverse(int dtype, int device, int uplo, int diag, int64_t n, void* A, int64_t lda,
+                                  void* stream) {
+    return MatrixInverseOp("TriangularInverse", dtype, device, uplo, n, A, lda, stream, [&](DistMatrix& M) {
+        ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "TriangularInverse: bad UnitOrNonUnit ", diag);
+        TriangularInverse(uplo, diag, M);
+    });
+}
+int elx_matrix_trtrmm(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
+    return MatrixInverseOp("Trtrmm", dtype, device, uplo, n, A, lda, stream,
+                           [&](DistMatrix& M) { Trtrmm(uplo, M); });
+}
+int elx_matrix_hpd_inverse(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
+    return MatrixInverseOp("HPDInverse", dtype, device, uplo, n, A, lda, stream,
+                           [&](DistMatrix& M) { HPDInverse(uplo, M); });
 }
 
 // ---- BLAS-1 --------------------------------------------------------------
@@ -832,6 +871,11 @@ int elx_cholesky_solve_after(int uplo, int orient, elx_dm_t A, elx_dm_t B) {
         cholesky::SolveAfter(uplo, orient, M(A), M(B));
     });
 }
+int elx_triangular_inverse(int uplo, int diag, elx_dm_t A) {
+    return Guard([&] { TriangularInverse(uplo, diag, M(A)); });
+}
+int elx_trtrmm(int uplo, elx_dm_t A, int conjugate) { return Guard([&] { Trtrmm(uplo, M(A), conjugate != 0); }); }
+int elx_hpd_inverse(int uplo, elx_dm_t A) { return Guard([&] { HPDInverse(uplo, M(A)); }); }
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {
     (void)conjugate;  // real types: Hemm == Symm
     return Guard([&] { Symm(side, uplo, alpha, M(A), M(B), beta, M(C)); });

@@ -466,6 +466,64 @@ void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* inf
     else cpu_cholesky(lower, n, static_cast<float*>(A), lda, info, col0);
 }
 
+// triang_inv::LVar3Unb (Inverse/Triangular/LVar3.hpp:17-43) on the stored
+// triangle: S(i,j), i >= j, is A(i,j) when lower and A(j,i) when upper (UVar3Unb
+// is the same loop on the transpose).  Divides without a singularity test.
+template <typename S>
+void cpu_trtri(bool lower, bool unit, Int n, S* A, Int lda) {
+    auto a = [&](Int i, Int j) -> S& { return lower ? A[i + j * lda] : A[j + i * lda]; };
+    for (Int j = 0; j < n; ++j) {
+        const S lambda = unit ? S(1) : a(j, j);
+        for (Int k = 0; k < j; ++k) a(j, k) /= -lambda;
+        for (Int k = 0; k < j; ++k)
+            for (Int i = j + 1; i < n; ++i) a(i, k) += a(i, j) * a(j, k);
+        if (!unit) {
+            for (Int i = j + 1; i < n; ++i) a(i, j) /= lambda;
+            a(j, j) = S(1) / lambda;
+        }
+    }
+}
+
+void TriangularInverse(Device dev, DType t, bool lower, bool unit, Int n, void* A, Int lda, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("TriangularInverse: only float and double are supported");
+    if (n <= 0) return;
+    if (dev == Device::GPU) {
+        ELX_REQUIRE(n <= kern::kTrtriMax, "TriangularInverse: block of ", n, " rows exceeds ", kern::kTrtriMax);
+        check(kern::trtri_block((int)t, lower, unit, n, A, lda, s), "trtri_block");
+        return;
+    }
+    if (t == DType::F64) cpu_trtri(lower, unit, n, static_cast<double*>(A), lda);
+    else cpu_trtri(lower, unit, n, static_cast<float*>(A), lda);
+}
+
+// trtrmm::LUnblocked (Trtrmm/Unblocked.hpp:16-64) on the stored triangle, S as
+// in cpu_trtri (UUnblocked is the same loop on the transpose)
+template <typename S>
+void cpu_trtrmm(bool lower, Int n, S* A, Int lda) {
+    auto a = [&](Int i, Int j) -> S& { return lower ? A[i + j * lda] : A[j + i * lda]; };
+    for (Int j = 0; j < n; ++j) {
+        for (Int k = 0; k < j; ++k) {
+            const S gamma = a(j, k);
+            for (Int i = k; i < j; ++i) a(i, k) += a(j, i) * gamma;
+        }
+        const S lambda = a(j, j);
+        for (Int k = 0; k < j; ++k) a(j, k) *= lambda;
+        a(j, j) = lambda * lambda;
+    }
+}
+
+void Trtrmm(Device dev, DType t, bool lower, Int n, void* A, Int lda, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("Trtrmm: only float and double are supported");
+    if (n <= 0) return;
+    if (dev == Device::GPU) {
+        ELX_REQUIRE(n <= kern::kTrtriMax, "Trtrmm: block of ", n, " rows exceeds ", kern::kTrtriMax);
+        check(kern::lauum_block((int)t, lower, n, A, lda, s), "lauum_block");
+        return;
+    }
+    if (t == DType::F64) cpu_trtrmm(lower, n, static_cast<double*>(A), lda);
+    else cpu_trtrmm(lower, n, static_cast<float*>(A), lda);
+}
+
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,
                        hipStream_t s) {
     check(kern::tri_inverse_batched((int)t, lower, trans, unit, nb, m, A, lda, W, s), "tri_inverse_batched");

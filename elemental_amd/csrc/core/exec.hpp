@@ -49,6 +49,13 @@ void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
 // still 0; a non-zero *info on entry makes the call a no-op.  info is device
 // memory for Device::GPU, host memory for Device::CPU.  f64/f32
 void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* info, int col0, hipStream_t s);
+// A := tri(A)^-1 in place on the uplo triangle of the n x n A (unit: the
+// diagonal is neither read nor written), n <= kern::kTrtriMax on the GPU
+// (triang_inv::LVar3Unb / UVar3Unb).  No singularity test.  f64/f32
+void TriangularInverse(Device dev, DType t, bool lower, bool unit, Int n, void* A, Int lda, hipStream_t s);
+// A := L^T L (lower) / U U^T (upper) in place on the uplo triangle, n <=
+// kern::kTrtriMax on the GPU (trtrmm::LUnblocked / UUnblocked).  f64/f32
+void Trtrmm(Device dev, DType t, bool lower, Int n, void* A, Int lda, hipStream_t s);
 // GPU only: W_b := op(A_bb)^-1 for every nb x nb diagonal block of the m x m A
 // (W_b at W + b*nb*nb, leading dimension nb), one launch
 void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m, const void* A, Int lda, void* W,

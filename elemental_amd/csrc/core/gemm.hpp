@@ -37,6 +37,14 @@ namespace cholesky {
 // B := A^-1 B from the factor in A's uplo triangle  (Cholesky/SolveAfter.hpp:78-107)
 void SolveAfter(int uplo, int orient, const DistMatrix& A, DistMatrix& B);
 }  // namespace cholesky
+// A := tri(A)^-1 in place on the uplo triangle (UNIT: the diagonal is neither read
+// nor written); no singularity test  (Inverse/Triangular.cpp:48-54)
+void TriangularInverse(int uplo, int diag, DistMatrix& A);
+// A := L^T L (LOWER) / U U^T (UPPER) in place on the uplo triangle  (Trtrmm.cpp)
+void Trtrmm(int uplo, DistMatrix& A, bool conjugate = false);
+// A := A^-1 on the uplo triangle of the HPD A: Cholesky, TriangularInverse,
+// Trtrmm; NonHPDMatrixError as Cholesky  (Inverse/HPD.cpp)
+void HPDInverse(int uplo, DistMatrix& A);
 // C := alpha A B + beta C (LEFT) / alpha B A + beta C (RIGHT), A symmetric (uplo stored)  (Symm.cpp:55-80)
 void Symm(int side, int uplo, double alpha, const DistMatrix& A, const DistMatrix& B, double beta, DistMatrix& C);
 

@@ -312,5 +312,15 @@ constexpr TrmmKRange trmm_krange(bool op_lower, i64 m, i64 i0, i64 bm, i64 bk = 
 // nothing.  f64 / f32.
 constexpr i64 kPotrfMax = 128;
 hipError_t potrf_block(int dtype, bool lower, i64 n, void* A, i64 lda, int* info, int col0, hipStream_t s);
+// The leaves of TriangularInverse and Trtrmm: one n x n block in place, n <=
+// kTrtriMax, one workgroup with the block held in LDS as potrf_block holds it.
+// Only the uplo triangle of A is read and written (unit: not the diagonal
+// either).  f64 / f32.
+//   trtri_block  A := tri(A)^-1.  No singularity test: an exact zero on a
+//                NON_UNIT diagonal leaves Inf / NaN.
+//   lauum_block  A := L^T L (lower) / U U^T (upper).
+constexpr i64 kTrtriMax = kPotrfMax;
+hipError_t trtri_block(int dtype, bool lower, bool unit, i64 n, void* A, i64 lda, hipStream_t s);
+hipError_t lauum_block(int dtype, bool lower, i64 n, void* A, i64 lda, hipStream_t s);
 }  // namespace kern
 }  // namespace elx

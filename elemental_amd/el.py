@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse","Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -377,6 +377,27 @@ def CholeskySolveAfter(uplo, orientation, A: DistMatrix, B: DistMatrix):
     """El::cholesky::SolveAfter(uplo, orientation, A, B) (Cholesky/SolveAfter.hpp:
     78-107): B := A^-1 B from the factor El::Cholesky left in A's uplo triangle."""
     call("elx_cholesky_solve_after", uplo, orientation, A.h, B.h)
+
+
+def TriangularInverse(uplo, diag, A: DistMatrix):
+    """El::TriangularInverse(uplo, diag, A) (Inverse/Triangular.cpp:48-54): A is
+    overwritten on its uplo triangle with tri(A)^-1; the other triangle, and with
+    UNIT the diagonal, is neither read nor written.  No singularity test: an exact
+    zero on a NON_UNIT diagonal leaves Inf / NaN."""
+    call("elx_triangular_inverse", uplo, diag, A.h)
+
+
+def Trtrmm(uplo, A: DistMatrix, conjugate: bool = False):
+    """El::Trtrmm(uplo, A, conjugate) (Trtrmm.cpp): A is overwritten on its uplo
+    triangle with L^T L (LOWER) or U U^T (UPPER)."""
+    call("elx_trtrmm", uplo, A.h, int(bool(conjugate)))
+
+
+def HPDInverse(uplo, A: DistMatrix):
+    """El::HPDInverse(uplo, A) (Inverse/HPD.cpp): the HPD A, its uplo triangle
+    stored, is overwritten on that triangle with A^-1 (Cholesky, TriangularInverse,
+    Trtrmm).  Raises NonHPDMatrixError as Cholesky does."""
+    call("elx_hpd_inverse", uplo, A.h)
 
 
 def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, conjugate: bool = False):

@@ -1076,6 +1076,72 @@ void HPDSolve(UpperOrLower uplo, Orientation orientation, const DistMatrix<T, U,
     DistMatrix<T, MC, MR, ELEMENT, D> ACopy(A);
     hpd_solve::Overwrite(uplo, orientation, ACopy, B);
 }
+// TriangularInverse (src/lapack_like/funcs/Inverse/Triangular.cpp): A := tri(A)^-1 in
+// place on the uplo triangle; the other triangle, and with UNIT the diagonal, is
+// neither read nor written.  No singularity test: an exact zero on a NON_UNIT
+// diagonal leaves Inf / NaN, as in the reference.  float and double.  A Matrix runs
+// the DistMatrix driver on its buffer, asynchronously on A's stream
+template <typename T>
+void TriangularInverse(UpperOrLower uplo, UnitOrNonUnit diag, AbstractDistMatrix<T>& A) {
+    detail::Check(elx_triangular_inverse(uplo, diag, A.h()));
+}
+template <typename T>
+void TriangularInverse(UpperOrLower uplo, UnitOrNonUnit diag, AbstractMatrix<T>& A) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_triangular_inverse(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, diag,
+                                                A.Height(), A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void TriangularInverse(UpperOrLower uplo, UnitOrNonUnit diag, Matrix<T, D>& A) {
+    TriangularInverse(uplo, diag, static_cast<AbstractMatrix<T>&>(A));
+}
+// on the local copy every rank holds (Triangular.cpp:56-62)
+template <typename T, Device D>
+void LocalTriangularInverse(UpperOrLower uplo, UnitOrNonUnit diag, DistMatrix<T, STAR, STAR, ELEMENT, D>& A) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_triangular_inverse(detail::TypeCode<T>::value, static_cast<int>(D), uplo, diag, A.Height(),
+                                                A.Buffer(), A.LDim() > 1 ? A.LDim() : 1, A.Stream()));
+}
+// Trtrmm (src/blas_like/level3/Trtrmm.cpp): A := L^T L (LOWER) or U U^T (UPPER) in
+// place on the uplo triangle; `conjugate` changes nothing for the real types.
+template <typename T>
+void Trtrmm(UpperOrLower uplo, AbstractDistMatrix<T>& A, bool conjugate = false) {
+    detail::Check(elx_trtrmm(uplo, A.h(), conjugate ? 1 : 0));
+}
+template <typename T>
+void Trtrmm(UpperOrLower uplo, AbstractMatrix<T>& A, bool /*conjugate*/ = false) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_trtrmm(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, A.Height(),
+                                    A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void Trtrmm(UpperOrLower uplo, Matrix<T, D>& A, bool conjugate = false) {
+    Trtrmm(uplo, static_cast<AbstractMatrix<T>&>(A), conjugate);
+}
+// HPDInverse (src/lapack_like/funcs/Inverse/HPD.cpp): A := A^-1 in place on the uplo
+// triangle of the Hermitian positive-definite A, as Cholesky, TriangularInverse,
+// Trtrmm.  NonHPDMatrixException as Cholesky throws it (A is then left as the
+// failed factorization left it); a Matrix's stream is synchronized as there
+template <typename T>
+void HPDInverse(UpperOrLower uplo, AbstractDistMatrix<T>& A) {
+    detail::Check(elx_hpd_inverse(uplo, A.h()));
+}
+template <typename T>
+void HPDInverse(UpperOrLower uplo, AbstractMatrix<T>& A) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_hpd_inverse(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, A.Height(),
+                                         A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void HPDInverse(UpperOrLower uplo, Matrix<T, D>& A) {
+    HPDInverse(uplo, static_cast<AbstractMatrix<T>&>(A));
+}
+template <typename T, Device D>
+void LocalHPDInverse(UpperOrLower uplo, DistMatrix<T, STAR, STAR, ELEMENT, D>& A) {
+    if (A.Height() != A.Width()) throw LogicError("A must be square");
+    detail::Check(elx_matrix_hpd_inverse(detail::TypeCode<T>::value, static_cast<int>(D), uplo, A.Height(), A.Buffer(),
+                                         A.LDim() > 1 ? A.LDim() : 1, A.Stream()));
+}
 template <typename T>
 void Symm(LeftOrRight side, UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& B,
           T beta, AbstractDistMatrix<T>& C, bool conjugate = false) {

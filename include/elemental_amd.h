@@ -209,6 +209,21 @@ int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int d
  * driver of elx_cholesky on the buffer.  ELX_ERR_NOT_HPD when a pivot is not > 0.
  * Synchronizes the stream (the status has to be read back).  f32/f64. */
 int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream);
+/* El::TriangularInverse on Matrix<T> (src/lapack_like/funcs/Inverse/Triangular.cpp):
+ * the n x n A := tri(A)^-1 in place on the uplo triangle; the other triangle, and
+ * with ELX_UNIT the diagonal, is neither read nor written.  No singularity test (an
+ * exact zero on a NON_UNIT diagonal leaves Inf / NaN).  Runs the blocked driver of
+ * elx_triangular_inverse on the buffer, asynchronously on the stream.  f32/f64. */
+int elx_matrix_triangular_inverse(int dtype, int device, int uplo, int diag, int64_t n, void* A, int64_t lda,
+                                  void* stream);
+/* El::Trtrmm on Matrix<T> (src/blas_like/level3/Trtrmm.cpp): the n x n A := L^T L
+ * (ELX_LOWER) or U U^T (ELX_UPPER) in place on the uplo triangle; asynchronous on the
+ * stream.  f32/f64. */
+int elx_matrix_trtrmm(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream);
+/* El::HPDInverse on Matrix<T> (src/lapack_like/funcs/Inverse/HPD.cpp): the n x n HPD
+ * A := A^-1 in place on the uplo triangle (Cholesky, TriangularInverse, Trtrmm).
+ * ELX_ERR_NOT_HPD as elx_matrix_cholesky; synchronizes the stream as it does.  f32/f64. */
+int elx_matrix_hpd_inverse(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -504,6 +519,18 @@ int64_t elx_cholesky_leaf_max(void);
 /* El::cholesky::SolveAfter (Cholesky/SolveAfter.hpp:78-107): B := A^-1 B from the
  * factor that elx_cholesky left in A's uplo triangle */
 int elx_cholesky_solve_after(int uplo, int orient, elx_dm_t A, elx_dm_t B);
+/* El::TriangularInverse on a DistMatrix (src/lapack_like/funcs/Inverse/Triangular.cpp):
+ * A := tri(A)^-1 in place on the uplo triangle (ELX_UNIT: the diagonal is neither read
+ * nor written); no singularity test; float and double */
+int elx_triangular_inverse(int uplo, int diag, elx_dm_t A);
+/* El::Trtrmm on a DistMatrix (src/blas_like/level3/Trtrmm.cpp): A := L^T L (ELX_LOWER)
+ * or U U^T (ELX_UPPER) in place on the uplo triangle; conjugate changes nothing for the
+ * real types; float and double */
+int elx_trtrmm(int uplo, elx_dm_t A, int conjugate);
+/* El::HPDInverse on a DistMatrix (src/lapack_like/funcs/Inverse/HPD.cpp): A := A^-1 in
+ * place on the uplo triangle; ELX_ERR_NOT_HPD (on every rank) from the Cholesky stage,
+ * which leaves A as the failed factorization left it; float and double */
+int elx_hpd_inverse(int uplo, elx_dm_t A);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
