@@ -86,6 +86,7 @@ _SIGS = {
     "elx_matrix_triangular_inverse": (_i, [_i, _i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_trtrmm": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_hpd_inverse": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
+    "elx_matrix_lu": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -182,6 +183,18 @@ _SIGS = {
     "elx_triangular_inverse": (_i, [_i, _i, _vp]),
     "elx_trtrmm": (_i, [_i, _vp, _i]),
     "elx_hpd_inverse": (_i, [_i, _vp]),
+    "elx_perm_create": (_i, [POINTER(c_void_p)]),
+    "elx_perm_destroy": (_i, [_vp]),
+    "elx_perm_make_identity": (_i, [_vp, _i64, _i]),
+    "elx_perm_height": (_i64, [_vp]),
+    "elx_perm_num_swaps": (_i64, [_vp]),
+    "elx_perm_swaps": (_i, [_vp, POINTER(c_int64)]),
+    "elx_perm_permute_rows": (_i, [_vp, _vp, _i]),
+    "elx_lu": (_i, [_vp, _vp]),
+    "elx_lu_solve_after": (_i, [_i, _vp, _vp, _vp]),
+    "elx_linear_solve": (_i, [_vp, _vp]),
+    "elx_lu_leaf_cols": (_i64, []),
+    "elx_lu_leaf_rows": (_i64, []),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),

@@ -6,6 +6,7 @@
 #include "core/distmatrix.hpp"
 #include "core/redist.hpp"
 #include "core/gemm.hpp"
+#include "core/lu.hpp"
 #include "core/random.hpp"
 #include "core/io.hpp"
 #include "core/exec.hpp"
@@ -15,6 +16,7 @@
 struct elx_comm_s { std::shared_ptr<elx::Comm> c; };
 struct elx_grid_s { std::shared_ptr<elx::Grid> g; };
 struct elx_dm_s { std::shared_ptr<elx::DistMatrix> m; };
+struct elx_perm_s { elx::Permutation p; };
 
 namespace elx {
 namespace {
@@ -31,6 +33,10 @@ Device ToDevice(int d) {
 DistMatrix& M(elx_dm_t h) {
     if (!h || !h->m) throw LogicError("null DistMatrix handle");
     return *h->m;
+}
+Permutation& Perm(elx_perm_t h) {
+    if (!h) throw LogicError("null Permutation handle");
+    return h->p;
 }
 void CheckOp(int o) {
     if (o != ELX_NORMAL && o != ELX_TRANSPOSE && o != ELX_ADJOINT) throw LogicError(Cat("invalid orientation ", o));
@@ -287,6 +293,31 @@ int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int
         M.Attach(n, n, 0, 0, A, lda, 0);
         if (d == Device::GPU) M.SetStream(DevStream(d, stream));
         Cholesky(uplo, M);
+    });
+}
+
+int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, int32_t* piv, void* stream) {
+    return Guard([&] {
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative LU dimension");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        if (t != DType::F64 && t != DType::F32) throw LogicError("LU: only float and double are supported");
+        CheckLd(lda, m, "A");
+        if (m == 0 || n == 0) return;
+        ELX_REQUIRE(piv != nullptr, "LU: null pivot array");
+        // the local driver on the buffer itself; the one read-back is the status
+        int column = 0;
+        if (d == Device::CPU) {
+            LocalLU(d, t, m, n, A, lda, piv, &column, 0, nullptr);
+        } else {
+            hipStream_t s = DevStream(d, stream);
+            Buffer info(Device::GPU, sizeof(int), s);
+            ELX_CHECK_HIP(hipMemsetAsync(info.data(), 0, sizeof(int), s));
+            LocalLU(d, t, m, n, A, lda, piv, static_cast<int*>(info.data()), 0, s);
+            ELX_CHECK_HIP(hipMemcpyAsync(&column, info.data(), sizeof(int), hipMemcpyDeviceToHost, s));
+            ELX_CHECK_HIP(hipStreamSynchronize(s));
+        }
+        if (column != 0) throw SingularMatrixError(column);
     });
 }
 
@@ -876,6 +907,47 @@ int elx_triangular_inverse(int uplo, int diag, elx_dm_t A) {
 }
 int elx_trtrmm(int uplo, elx_dm_t A, int conjugate) { return Guard([&] { Trtrmm(uplo, M(A), conjugate != 0); }); }
 int elx_hpd_inverse(int uplo, elx_dm_t A) { return Guard([&] { HPDInverse(uplo, M(A)); }); }
+int elx_perm_create(elx_perm_t* P) {
+    return Guard([&] {
+        ELX_REQUIRE(P != nullptr, "null Permutation handle");
+        *P = new elx_perm_s{};
+    });
+}
+int elx_perm_destroy(elx_perm_t P) { return Guard([&] { delete P; }); }
+int elx_perm_make_identity(elx_perm_t P, int64_t n, int device) {
+    return Guard([&] { Perm(P).MakeIdentity(n, ToDevice(device)); });
+}
+int64_t elx_perm_height(elx_perm_t P) { return P ? P->p.Height() : -1; }
+int64_t elx_perm_num_swaps(elx_perm_t P) { return P ? P->p.NumSwaps() : -1; }
+int elx_perm_swaps(elx_perm_t P, int64_t* dests) {
+    return Guard([&] {
+        const std::vector<int64_t> d = Perm(P).SwapDests();
+        ELX_REQUIRE(d.empty() || dests != nullptr, "null output array");
+        std::copy(d.begin(), d.end(), dests);
+    });
+}
+int elx_perm_permute_rows(elx_perm_t P, elx_dm_t B, int inverse) {
+    return Guard([&] {
+        if (inverse) Perm(P).InversePermuteRows(M(B));
+        else Perm(P).PermuteRows(M(B));
+    });
+}
+int elx_lu(elx_dm_t A, elx_perm_t P) { return Guard([&] { LU(M(A), Perm(P)); }); }
+int elx_lu_solve_after(int orient, elx_dm_t A, elx_perm_t P, elx_dm_t B) {
+    return Guard([&] {
+        CheckOp(orient);
+        ELX_REQUIRE(&M(A).G() == &M(B).G(), "SolveAfter: matrices on different grids");
+        lu::SolveAfter(orient, M(A), Perm(P), M(B));
+    });
+}
+int elx_linear_solve(elx_dm_t A, elx_dm_t B) {
+    return Guard([&] {
+        ELX_REQUIRE(&M(A).G() == &M(B).G(), "LinearSolve: matrices on different grids");
+        LinearSolve(M(A), M(B));
+    });
+}
+int64_t elx_lu_leaf_cols(void) { return kern::kGetrfLeafCols; }
+int64_t elx_lu_leaf_rows(void) { return kern::kGetrfLeafRows; }
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {
     (void)conjugate;  // real types: Hemm == Symm
     return Guard([&] { Symm(side, uplo, alpha, M(A), M(B), beta, M(C)); });

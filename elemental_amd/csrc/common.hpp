@@ -25,6 +25,9 @@ struct NoDeviceError : std::runtime_error { using std::runtime_error::runtime_er
 // El::SingularMatrixException (include/El/core/environment/decl.hpp:209-214)
 struct SingularMatrixError : std::runtime_error {
     SingularMatrixError() : std::runtime_error("Matrix was singular") {}
+    // LU: the 1-based column whose pivot was exactly zero
+    explicit SingularMatrixError(int col)
+        : std::runtime_error("Matrix was singular: zero pivot in column " + std::to_string(col)) {}
 };
 // El::NonHPDMatrixException (include/El/core/environment/decl.hpp); column: the
 // 1-based column whose pivot was not positive

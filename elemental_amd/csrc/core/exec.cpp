@@ -466,6 +466,75 @@ void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* inf
     else cpu_cholesky(lower, n, static_cast<float*>(A), lda, info, col0);
 }
 
+// lu::Panel (LU/Panel.hpp): per column the entry of largest magnitude at or
+// below the diagonal (the first of equals; a NaN never beats a number), the row
+// swap across the panel, the scaling and the rank-one update
+template <typename S>
+void cpu_lu_panel(Int m, Int w, S* A, Int lda, int* piv, int row_off, int* info, int col0) {
+    for (Int j = 0; j < w; ++j) {
+        S* aj = A + j * lda;
+        Int p = -1;
+        S best = S(-1);
+        for (Int i = j; i < m; ++i) {
+            const S v = std::fabs(aj[i]);
+            if (v > best) { best = v; p = i; }
+        }
+        if (!(best > S(0))) {
+            if (*info == 0) *info = col0 + (int)j + 1;
+            return;
+        }
+        piv[j] = row_off + (int)p;
+        if (p != j)
+            for (Int k = 0; k < w; ++k) std::swap(A[j + k * lda], A[p + k * lda]);
+        const S d = aj[j];
+        for (Int i = j + 1; i < m; ++i) aj[i] = aj[i] / d;
+        for (Int k = j + 1; k < w; ++k) {
+            S* ak = A + k * lda;
+            const S u = ak[j];
+            for (Int i = j + 1; i < m; ++i) ak[i] -= aj[i] * u;
+        }
+    }
+}
+
+size_t LUWorkBytes(Device dev, Int m) { return dev == Device::GPU ? kern::getrf_work_bytes(m) : 0; }
+
+void LU(Device dev, DType t, Int m, Int w, void* A, Int lda, int* piv, int row_off, void* work, int* info, int col0,
+        hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("LU: only float and double are supported");
+    if (m <= 0 || w <= 0) return;
+    ELX_REQUIRE(w <= kern::kGetrfLeafCols && w <= m, "LU: a leaf of ", m, " x ", w);
+    if (dev == Device::GPU) {
+        check(kern::getrf_leaf((int)t, m, w, A, lda, piv, row_off, work, info, col0, s), "getrf_leaf");
+        return;
+    }
+    if (*info != 0) return;
+    if (t == DType::F64) cpu_lu_panel(m, w, static_cast<double*>(A), lda, piv, row_off, info, col0);
+    else cpu_lu_panel(m, w, static_cast<float*>(A), lda, piv, row_off, info, col0);
+}
+
+template <typename S>
+void cpu_laswp(Int m, Int n, S* A, Int lda, const int* piv, Int k0, Int k1, Int voff, bool inverse) {
+    for (Int q = k0; q < k1; ++q) {
+        const Int k = inverse ? k0 + k1 - 1 - q : q, p = (Int)piv[k] - voff;
+        if (p == k || p < 0 || p >= m || k >= m) continue;
+        for (Int c = 0; c < n; ++c) std::swap(A[k + c * lda], A[p + c * lda]);
+    }
+}
+
+void Laswp(Device dev, DType t, Int m, Int n, void* A, Int lda, const int* piv, Int k0, Int k1, Int voff, bool inverse,
+           const int* info, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("Laswp: only float and double are supported");
+    if (m <= 0 || n <= 0 || k1 <= k0) return;
+    if (dev == Device::GPU) {
+        check(kern::laswp((int)t, m, n, A, lda, piv, k0, k1, voff, inverse, info, s), "laswp");
+        return;
+    }
+    if (info && *info != 0) return;
+    // moved as integers: a swap through a float register may quieten a NaN on the host
+    if (t == DType::F64) cpu_laswp(m, n, static_cast<uint64_t*>(A), lda, piv, k0, k1, voff, inverse);
+    else cpu_laswp(m, n, static_cast<uint32_t*>(A), lda, piv, k0, k1, voff, inverse);
+}
+
 // triang_inv::LVar3Unb (Inverse/Triangular/LVar3.hpp:17-43) on the stored
 // triangle: S(i,j), i >= j, is A(i,j) when lower and A(j,i) when upper (UVar3Unb
 // is the same loop on the transpose).  Divides without a singularity test.

@@ -49,6 +49,21 @@ void Trmm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
 // still 0; a non-zero *info on entry makes the call a no-op.  info is device
 // memory for Device::GPU, host memory for Device::CPU.  f64/f32
 void Cholesky(Device dev, DType t, bool lower, Int n, void* A, Int lda, int* info, int col0, hipStream_t s);
+// P A = L U of the m x w column panel A in place, w <= kern::kGetrfLeafCols <= m
+// (lu::Panel, LU/Panel.hpp): piv[j] = row_off + the row that was swapped with row
+// j at step j.  The largest |value| pivots, ties to the smallest row, a NaN never
+// beats a number.  An exactly zero pivot (or nothing but zeros and NaNs left)
+// stops it and stores col0 + j + 1 in *info if that is still 0; a non-zero
+// *info on entry makes the call a no-op.  piv, info and work (LUWorkBytes(dev,
+// m) bytes, the GPU kernels' scratch) live in the matrix's memory space.  On
+// the GPU this is launches and nothing else.  f64/f32
+size_t LUWorkBytes(Device dev, Int m);
+void LU(Device dev, DType t, Int m, Int w, void* A, Int lda, int* piv, int row_off, void* work, int* info, int col0,
+        hipStream_t s);
+// rows k and piv[k] - voff of the m x n A swapped for k = k0..k1-1 (inverse: in
+// the opposite order); bit-exact.  info (may be null): non-zero makes it a no-op
+void Laswp(Device dev, DType t, Int m, Int n, void* A, Int lda, const int* piv, Int k0, Int k1, Int voff, bool inverse,
+           const int* info, hipStream_t s);
 // A := tri(A)^-1 in place on the uplo triangle of the n x n A (unit: the
 // diagonal is neither read nor written), n <= kern::kTrtriMax on the GPU
 // (triang_inv::LVar3Unb / UVar3Unb).  No singularity test.  f64/f32

@@ -322,5 +322,38 @@ hipError_t potrf_block(int dtype, bool lower, i64 n, void* A, i64 lda, int* info
 constexpr i64 kTrtriMax = kPotrfMax;
 hipError_t trtri_block(int dtype, bool lower, bool unit, i64 n, void* A, i64 lda, hipStream_t s);
 hipError_t lauum_block(int dtype, bool lower, i64 n, void* A, i64 lda, hipStream_t s);
+// LU with partial pivoting of one m x w column panel in place (getrf.hip), w <=
+// kGetrfLeafCols, m >= w: kGetrfLeafRows rows per workgroup, one launch per
+// column step (w + 2 launches, nothing else on the host).  piv[0..w) receives
+// the LAPACK swap sequence (row j was swapped with row piv[j] - row_off), each
+// entry offset by row_off.  work: getrf_work_bytes(m) bytes of device scratch.
+// An exactly zero pivot (or a column with nothing but zeros and NaNs left)
+// stores col0 + j + 1 in the device word *info if it is still 0; launches that
+// find *info != 0 do nothing.  f64 / f32.
+constexpr int kGetrfLeafCols = 16, kGetrfLeafRows = 256;
+size_t getrf_work_bytes(i64 m);
+hipError_t getrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, int* piv, int row_off, void* work, int* info,
+                      int col0, hipStream_t s);
+// Rows k and piv[k] - voff of the m x ncols A swapped for k = k0..k1-1 in that
+// order (inverse: in the opposite order, which undoes it); piv is device memory,
+// a pivot outside [0, m) is skipped.  info (may be null): a non-zero device word
+// makes the launch a no-op.  Moves bits: f64 also serves any 8-byte type.
+hipError_t laswp(int dtype, i64 m, i64 ncols, void* A, i64 lda, const int* piv, i64 k0, i64 k1, i64 voff,
+                 bool inverse, const int* info, hipStream_t s);
+// The run of swaps k0..k0+nbr-1 on a matrix whose rows are dealt over `stride`
+// process rows (row P on process row (P + align) % stride, local row P / stride),
+// with the pivots in device memory throughout.  Slot q < nbr stands for row
+// k0 + q, slot nbr + q for row piv[k0 + q].
+//   perm_meta   meta[q]: the first slot standing for the same row (-1: a row
+//               outside [0, m)); meta[2 nbr + q]: the process row owning it
+//   perm_move   pack the owned slots of the local block A into buf (2 nbr x lw,
+//               leading dimension 2 nbr), or (scatter) unpack them from it
+//   perm_apply  the swaps on the all-gathered buffers (`stride` parts of 2 nbr x
+//               lw in process-row order), one thread per local column
+// Bits are moved, never computed on.
+hipError_t perm_meta(const int* piv, i64 k0, i64 nbr, i64 m, int stride, int align, int* meta, hipStream_t s);
+hipError_t perm_move(size_t elem_size, bool scatter, const int* piv, const int* meta, i64 k0, i64 nbr, int stride,
+                     int rank, void* A, i64 lda, i64 lw, void* buf, hipStream_t s);
+hipError_t perm_apply(size_t elem_size, const int* meta, i64 nbr, bool inverse, void* gathered, i64 lw, hipStream_t s);
 }  // namespace kern
 }  // namespace elx

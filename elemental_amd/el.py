@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse","Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -398,6 +398,79 @@ def HPDInverse(uplo, A: DistMatrix):
     stored, is overwritten on that triangle with A^-1 (Cholesky, TriangularInverse,
     Trtrmm).  Raises NonHPDMatrixError as Cholesky does."""
     call("elx_hpd_inverse", uplo, A.h)
+
+
+SingularMatrixError = L.SingularMatrixError
+
+
+class Permutation:
+    """El::Permutation / El::DistPermutation as a swap sequence: rows k and
+    swap_dests()[k] are swapped for k = 0, 1, ... (the LAPACK ipiv, 0-based).  The
+    sequence lives where the matrices live (device memory for GPU matrices); the
+    host copies below are made only when asked for."""
+
+    def __init__(self):
+        h = c_void_p()
+        call("elx_perm_create", byref(h))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().elx_perm_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def MakeIdentity(self, n: int, device: int = CPU):
+        call("elx_perm_make_identity", self.h, n, device)
+        return self
+
+    def Height(self) -> int:
+        return int(lib().elx_perm_height(self.h))
+
+    def swap_dests(self) -> np.ndarray:
+        """The swap destinations (int64), one per pivot."""
+        out = np.zeros(int(lib().elx_perm_num_swaps(self.h)), dtype=np.int64)
+        call("elx_perm_swaps", self.h, out.ctypes.data_as(ctypes.POINTER(c_int64)))
+        return out
+
+    def explicit_vector(self) -> np.ndarray:
+        """v with (P B)[i, :] = B[v[i], :]."""
+        v = np.arange(self.Height(), dtype=np.int64)
+        for k, d in enumerate(self.swap_dests()):
+            v[k], v[d] = v[d], v[k]
+        return v
+
+    def PermuteRows(self, B: DistMatrix):
+        """B := P B, bit-exact (any grid; [MC,MR] in place, others through a proxy)."""
+        call("elx_perm_permute_rows", self.h, B.h, 0)
+
+    def InversePermuteRows(self, B: DistMatrix):
+        """B := P^-1 B, bit-exact."""
+        call("elx_perm_permute_rows", self.h, B.h, 1)
+
+
+def LU(A: DistMatrix) -> Permutation:
+    """El::LU(A, P) (src/lapack_like/factor/LU.cpp:88-131): A is overwritten with
+    its factors (L unit lower, U upper, P A = L U, partial pivoting) and P is
+    returned.  Raises SingularMatrixError (on every rank; the message names the
+    1-based column) when a pivot is exactly zero; A is then unspecified."""
+    P = Permutation()
+    call("elx_lu", A.h, P.h)
+    return P
+
+
+def LUSolveAfter(orientation, A: DistMatrix, P: Permutation, B: DistMatrix):
+    """El::lu::SolveAfter(orientation, A, P, B) (LU/SolveAfter.hpp:94-121):
+    B := op(A)^-1 B from the factors El::LU left in A and P."""
+    call("elx_lu_solve_after", orientation, A.h, P.h, B.h)
+
+
+def LinearSolve(A: DistMatrix, B: DistMatrix):
+    """El::LinearSolve(A, B) (src/lapack_like/solve/Linear.cpp): B := A^-1 B; A is
+    factored in a copy and left as it was."""
+    call("elx_linear_solve", A.h, B.h)
 
 
 def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, conjugate: bool = False):

@@ -1076,6 +1076,103 @@ void HPDSolve(UpperOrLower uplo, Orientation orientation, const DistMatrix<T, U,
     DistMatrix<T, MC, MR, ELEMENT, D> ACopy(A);
     hpd_solve::Overwrite(uplo, orientation, ACopy, B);
 }
+// Permutation / DistPermutation (include/El/core/Permutation.hpp, DistPermutation.hpp)
+// as a swap sequence: rows k and SwapDests()[k] are swapped for k = 0, 1, ... (the
+// LAPACK ipiv, 0-based).  The sequence lives where the matrices it came from live
+// (device memory for Device::GPU); SwapDests / ExplicitVector / Parity copy it to
+// the host.  PermuteRows is bit-exact.  One class serves both names.
+namespace detail {
+// a Matrix's buffer as the local block of a 1x1-grid [MC,MR] DistMatrix handle.  The
+// grid is made per call and lives exactly as long as the handle (nothing static
+// outlives Finalize)
+template <typename T>
+std::shared_ptr<elx_dm_s> AttachLocal(AbstractMatrix<T>& A) {
+    auto self = std::make_shared<Grid>(mpi::COMM_SELF());
+    elx_dm_t h = nullptr;
+    Check(elx_dm_create(&h, self->Handle(), TypeCode<T>::value, ELX_MC, ELX_MR, static_cast<int>(A.GetDevice()), 0));
+    std::shared_ptr<elx_dm_s> p(h, [self](elx_dm_s* q) { if (q) elx_dm_destroy(q); });
+    Check(elx_dm_attach(h, A.Height(), A.Width(), 0, 0, A.Buffer(), A.LDim() > 1 ? A.LDim() : 1, 0));
+    if (A.GetDevice() == Device::GPU) Check(elx_dm_set_stream(h, A.Stream()));
+    return p;
+}
+}  // namespace detail
+class Permutation {
+public:
+    Permutation() {
+        elx_perm_t p = nullptr;
+        detail::Check(elx_perm_create(&p));
+        p_.reset(p, [](elx_perm_s* q) { if (q) elx_perm_destroy(q); });
+    }
+    void MakeIdentity(Int n, Device device = Device::CPU) {
+        detail::Check(elx_perm_make_identity(h(), n, static_cast<int>(device)));
+    }
+    Int Height() const { return elx_perm_height(h()); }
+    template <typename T> void PermuteRows(AbstractDistMatrix<T>& B) const {
+        detail::Check(elx_perm_permute_rows(h(), B.h(), 0));
+    }
+    template <typename T> void InversePermuteRows(AbstractDistMatrix<T>& B) const {
+        detail::Check(elx_perm_permute_rows(h(), B.h(), 1));
+    }
+    template <typename T> void PermuteRows(AbstractMatrix<T>& B) const {
+        detail::Check(elx_perm_permute_rows(h(), detail::AttachLocal(B).get(), 0));
+    }
+    template <typename T> void InversePermuteRows(AbstractMatrix<T>& B) const {
+        detail::Check(elx_perm_permute_rows(h(), detail::AttachLocal(B).get(), 1));
+    }
+    std::vector<Int> SwapDests() const {
+        std::vector<std::int64_t> d(static_cast<size_t>(elx_perm_num_swaps(h())));
+        detail::Check(elx_perm_swaps(h(), d.data()));
+        return std::vector<Int>(d.begin(), d.end());
+    }
+    std::vector<Int> ExplicitVector() const {  // (P B)(i, :) = B(v[i], :)
+        const std::vector<Int> d = SwapDests();
+        std::vector<Int> v(static_cast<size_t>(Height()));
+        for (size_t i = 0; i < v.size(); ++i) v[i] = static_cast<Int>(i);
+        for (size_t k = 0; k < d.size(); ++k) std::swap(v[k], v[static_cast<size_t>(d[k])]);
+        return v;
+    }
+    bool Parity() const {  // true: an odd permutation
+        const std::vector<Int> d = SwapDests();
+        bool odd = false;
+        for (size_t k = 0; k < d.size(); ++k) odd ^= d[k] != static_cast<Int>(k);
+        return odd;
+    }
+    elx_perm_t h() const { return p_.get(); }
+
+private:
+    std::shared_ptr<elx_perm_s> p_;
+};
+using DistPermutation = Permutation;
+// LU with partial pivoting (src/lapack_like/factor/LU.cpp:88-131): P A = L U in place
+// (L unit lower, U upper), P receiving the min(m, n) swaps.  SingularMatrixException
+// (on every rank, naming the 1-based column) when a pivot is exactly zero; A and P
+// are then unspecified.  float and double.  A Matrix runs the driver on its buffer
+// (on A's stream, which is synchronized: the status has to be read back)
+template <typename T>
+void LU(AbstractDistMatrix<T>& A, DistPermutation& P) {
+    detail::Check(elx_lu(A.h(), P.h()));
+}
+template <typename T>
+void LU(AbstractMatrix<T>& A, Permutation& P) {
+    detail::Check(elx_lu(detail::AttachLocal(A).get(), P.h()));
+}
+template <typename T, Device D>
+void LU(Matrix<T, D>& A, Permutation& P) {
+    LU(static_cast<AbstractMatrix<T>&>(A), P);
+}
+namespace lu {
+// B := op(A)^-1 B from the factors LU left in A and P (LU/SolveAfter.hpp:94-121)
+template <typename T>
+void SolveAfter(Orientation orientation, const AbstractDistMatrix<T>& A, const DistPermutation& P,
+                AbstractDistMatrix<T>& B) {
+    detail::Check(elx_lu_solve_after(orientation, A.h(), P.h(), B.h()));
+}
+}  // namespace lu
+// B := A^-1 B; A is factored in a copy (src/lapack_like/solve/Linear.cpp)
+template <typename T>
+void LinearSolve(const AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& B) {
+    detail::Check(elx_linear_solve(A.h(), B.h()));
+}
 // TriangularInverse (src/lapack_like/funcs/Inverse/Triangular.cpp): A := tri(A)^-1 in
 // place on the uplo triangle; the other triangle, and with UNIT the diagonal, is
 // neither read nor written.  No singularity test: an exact zero on a NON_UNIT

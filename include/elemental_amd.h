@@ -224,6 +224,12 @@ int elx_matrix_trtrmm(int dtype, int device, int uplo, int64_t n, void* A, int64
  * A := A^-1 in place on the uplo triangle (Cholesky, TriangularInverse, Trtrmm).
  * ELX_ERR_NOT_HPD as elx_matrix_cholesky; synchronizes the stream as it does.  f32/f64. */
 int elx_matrix_hpd_inverse(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream);
+/* El::LU on Matrix<T> (src/lapack_like/factor/LU.cpp): P A = L U of the m x n A in
+ * place with partial pivoting; piv receives min(m, n) int32 entries in the matrix's
+ * memory space, row j was swapped with row piv[j] (0-based).  ELX_ERR_SINGULAR when a
+ * pivot is exactly zero (A and piv are then unspecified).  Synchronizes the stream
+ * (the status has to be read back).  f32/f64. */
+int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, int32_t* piv, void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -531,6 +537,32 @@ int elx_trtrmm(int uplo, elx_dm_t A, int conjugate);
  * place on the uplo triangle; ELX_ERR_NOT_HPD (on every rank) from the Cholesky stage,
  * which leaves A as the failed factorization left it; float and double */
 int elx_hpd_inverse(int uplo, elx_dm_t A);
+/* El::Permutation / El::DistPermutation as a swap sequence (rows k and dest[k] swapped
+ * for k = 0, 1, ...: the LAPACK ipiv, 0-based).  The sequence lives in host memory for
+ * ELX_DEVICE_CPU and in device memory for ELX_DEVICE_GPU; elx_lu resets it to A's
+ * height and device.  elx_perm_swaps copies the elx_perm_num_swaps destinations to a
+ * host array (synchronizing the permutation's stream).  elx_perm_permute_rows:
+ * B := P B (inverse = 0) or P^-1 B, bit-exact, any grid; float and double. */
+typedef struct elx_perm_s* elx_perm_t;
+int elx_perm_create(elx_perm_t* P);
+int elx_perm_destroy(elx_perm_t P);
+int elx_perm_make_identity(elx_perm_t P, int64_t n, int device);
+int64_t elx_perm_height(elx_perm_t P);
+int64_t elx_perm_num_swaps(elx_perm_t P);
+int elx_perm_swaps(elx_perm_t P, int64_t* dests);
+int elx_perm_permute_rows(elx_perm_t P, elx_dm_t B, int inverse);
+/* El::LU with partial pivoting (src/lapack_like/factor/LU.cpp:88-131): P A = L U in
+ * place, L unit lower and U upper, min(m, n) swaps in P.  ELX_ERR_SINGULAR (on every
+ * rank; the message names the 1-based column) when a pivot is exactly zero; A and P
+ * are then unspecified.  float and double */
+int elx_lu(elx_dm_t A, elx_perm_t P);
+/* El::lu::SolveAfter (LU/SolveAfter.hpp:94-121): B := op(A)^-1 B from elx_lu's A and P */
+int elx_lu_solve_after(int orient, elx_dm_t A, elx_perm_t P, elx_dm_t B);
+/* El::LinearSolve (src/lapack_like/solve/Linear.cpp): B := A^-1 B; A is left as it was */
+int elx_linear_solve(elx_dm_t A, elx_dm_t B);
+/* the leaf kernel's panel width and its rows per workgroup (kGetrfLeafCols, kGetrfLeafRows) */
+int64_t elx_lu_leaf_cols(void);
+int64_t elx_lu_leaf_rows(void);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
