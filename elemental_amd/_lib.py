@@ -87,6 +87,7 @@ _SIGS = {
     "elx_matrix_trtrmm": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_hpd_inverse": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_lu": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "elx_matrix_qr": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -195,6 +196,14 @@ _SIGS = {
     "elx_linear_solve": (_i, [_vp, _vp]),
     "elx_lu_leaf_cols": (_i64, []),
     "elx_lu_leaf_rows": (_i64, []),
+    "elx_qr": (_i, [_vp, _vp, _vp]),
+    "elx_qr_apply_q": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "elx_qr_solve_after": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "elx_qr_explicit": (_i, [_vp, _vp]),
+    "elx_qr_explicit_triang": (_i, [_vp]),
+    "elx_least_squares": (_i, [_i, _vp, _vp, _vp]),
+    "elx_qr_leaf_cols": (_i64, []),
+    "elx_qr_leaf_rows": (_i64, []),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),

@@ -7,6 +7,7 @@
 #include "core/redist.hpp"
 #include "core/gemm.hpp"
 #include "core/lu.hpp"
+#include "core/qr.hpp"
 #include "core/random.hpp"
 #include "core/io.hpp"
 #include "core/exec.hpp"
@@ -318,6 +319,22 @@ int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
             ELX_CHECK_HIP(hipStreamSynchronize(s));
         }
         if (column != 0) throw SingularMatrixError(column);
+    });
+}
+
+int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, void* tau, void* sig,
+                  void* stream) {
+    return Guard([&] {
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative QR dimension");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+        CheckLd(lda, m, "A");
+        if (m == 0 || n == 0) return;
+        ELX_REQUIRE(A != nullptr, "QR: null matrix");
+        ELX_REQUIRE(tau != nullptr && sig != nullptr, "QR: null scalar or signature array");
+        // the local driver on the buffer itself: launches on the stream, no read-back
+        LocalQR(d, t, m, n, A, lda, tau, sig, d == Device::GPU ? DevStream(d, stream) : nullptr);
     });
 }
 
@@ -948,6 +965,29 @@ int elx_linear_solve(elx_dm_t A, elx_dm_t B) {
 }
 int64_t elx_lu_leaf_cols(void) { return kern::kGetrfLeafCols; }
 int64_t elx_lu_leaf_rows(void) { return kern::kGetrfLeafRows; }
+int elx_qr(elx_dm_t A, elx_dm_t t, elx_dm_t d) { return Guard([&] { QR(M(A), M(t), M(d)); }); }
+int elx_qr_apply_q(int side, int orient, elx_dm_t A, elx_dm_t t, elx_dm_t d, elx_dm_t B) {
+    return Guard([&] {
+        CheckOp(orient);
+        qr::ApplyQ(side, orient, M(A), M(t), M(d), M(B));
+    });
+}
+int elx_qr_solve_after(int orient, elx_dm_t A, elx_dm_t t, elx_dm_t d, elx_dm_t B, elx_dm_t X) {
+    return Guard([&] {
+        CheckOp(orient);
+        qr::SolveAfter(orient, M(A), M(t), M(d), M(B), M(X));
+    });
+}
+int elx_qr_explicit(elx_dm_t A, elx_dm_t R) { return Guard([&] { qr::Explicit(M(A), M(R)); }); }
+int elx_qr_explicit_triang(elx_dm_t A) { return Guard([&] { qr::ExplicitTriang(M(A)); }); }
+int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X) {
+    return Guard([&] {
+        CheckOp(orient);
+        LeastSquares(orient, M(A), M(B), M(X));
+    });
+}
+int64_t elx_qr_leaf_cols(void) { return kern::kGeqrfLeafCols; }
+int64_t elx_qr_leaf_rows(void) { return kern::kGeqrfLeafRows; }
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {
     (void)conjugate;  // real types: Hemm == Symm
     return Guard([&] { Symm(side, uplo, alpha, M(A), M(B), beta, M(C)); });

@@ -535,6 +535,119 @@ void Laswp(Device dev, DType t, Int m, Int n, void* A, Int lda, const int* piv, 
     else cpu_laswp(m, n, static_cast<uint32_t*>(A), lda, piv, k0, k1, voff, inverse);
 }
 
+// qr::PanelHouseholder with reflector::Col, column by column; the norm as the
+// scaled pair (max |a|, sum (a / max)^2), the dots with the already scaled u
+// (|u_i| <= 1), sums in double
+template <typename S>
+void cpu_qr_panel(Int m, Int w, S* A, Int lda, S* tau, S* sig) {
+    const Int k = std::min(m, w);
+    for (Int j = 0; j < k; ++j) {
+        S* aj = A + j * lda;
+        double mx = 0.0;
+        for (Int i = j + 1; i < m; ++i) {
+            const double v = std::fabs((double)aj[i]);
+            if (v > mx || v != v) mx = v;  // a NaN stays
+        }
+        const double alpha = (double)aj[j];
+        double beta, t;
+        if (mx == 0.0) {
+            beta = -alpha;
+            t = 2.0;
+            for (Int i = j + 1; i < m; ++i) aj[i] = S(0);
+        } else {
+            double ssq = 0.0;
+            for (Int i = j + 1; i < m; ++i) {
+                const double r = (double)aj[i] / mx;
+                ssq += r * r;
+            }
+            const double nrm = std::hypot(alpha, mx * std::sqrt(ssq));
+            beta = alpha <= 0.0 ? nrm : -nrm;
+            t = (double)(S)((beta - alpha) / beta);
+            const double denom = alpha - beta;
+            for (Int i = j + 1; i < m; ++i) aj[i] = (S)((double)aj[i] / denom);
+        }
+        const double d = beta >= 0.0 ? 1.0 : -1.0;
+        for (Int c = j + 1; c < w; ++c) {
+            S* ac = A + c * lda;
+            double z = (double)ac[j];
+            for (Int i = j + 1; i < m; ++i) z += (double)aj[i] * (double)ac[i];
+            for (Int i = j + 1; i < m; ++i) ac[i] = (S)((double)ac[i] - t * (double)aj[i] * z);
+            ac[j] = (S)(d * ((double)ac[j] - t * z));
+        }
+        aj[j] = (S)(beta * d);
+        tau[j] = (S)t;
+        sig[j] = (S)d;
+    }
+}
+
+size_t QRWorkBytes(Device dev, Int m) { return dev == Device::GPU ? kern::geqrf_work_bytes(m) : 0; }
+
+void QR(Device dev, DType t, Int m, Int w, void* A, Int lda, void* tau, void* sig, void* work, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+    if (m <= 0 || w <= 0) return;
+    ELX_REQUIRE(w <= kern::kGeqrfLeafCols, "QR: a leaf of ", m, " x ", w);
+    if (dev == Device::GPU) {
+        check(kern::geqrf_leaf((int)t, m, w, A, lda, tau, sig, work, s), "geqrf_leaf");
+        return;
+    }
+    if (t == DType::F64)
+        cpu_qr_panel(m, w, static_cast<double*>(A), lda, static_cast<double*>(tau), static_cast<double*>(sig));
+    else cpu_qr_panel(m, w, static_cast<float*>(A), lda, static_cast<float*>(tau), static_cast<float*>(sig));
+}
+
+template <typename S>
+void cpu_qr_explicit_u(Int m, Int nb, const S* A, Int lda, S* U, Int ldu) {
+    for (Int c = 0; c < nb; ++c)
+        for (Int i = 0; i < m; ++i) U[i + c * ldu] = i > c ? A[i + c * lda] : (i == c ? S(1) : S(0));
+}
+
+void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+    if (m <= 0 || nb <= 0) return;
+    if (dev == Device::GPU) {
+        check(kern::qr_explicit_u((int)t, m, nb, A, lda, U, ldu, s), "qr_explicit_u");
+        return;
+    }
+    if (t == DType::F64) cpu_qr_explicit_u(m, nb, static_cast<const double*>(A), lda, static_cast<double*>(U), ldu);
+    else cpu_qr_explicit_u(m, nb, static_cast<const float*>(A), lda, static_cast<float*>(U), ldu);
+}
+
+template <typename S>
+void cpu_qr_fix_t(Int nb, S* T, Int ldt, const S* tau) {
+    for (Int c = 0; c < nb; ++c) {
+        for (Int i = 0; i < c; ++i) T[i + c * ldt] = S(0);
+        T[c + c * ldt] = S(1) / tau[c];
+    }
+}
+
+void QRFixT(Device dev, DType t, Int nb, void* S, Int lds, const void* tau, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+    if (nb <= 0) return;
+    if (dev == Device::GPU) {
+        check(kern::qr_fix_t((int)t, nb, S, lds, tau, s), "qr_fix_t");
+        return;
+    }
+    if (t == DType::F64) cpu_qr_fix_t(nb, static_cast<double*>(S), lds, static_cast<const double*>(tau));
+    else cpu_qr_fix_t(nb, static_cast<float*>(S), lds, static_cast<const float*>(tau));
+}
+
+template <typename S>
+void cpu_row_scale(Int m, Int n, S* A, Int lda, const S* sig, Int i0, Int is) {
+    for (Int c = 0; c < n; ++c)
+        for (Int i = 0; i < m; ++i) A[i + c * lda] *= sig[i0 + i * is];
+}
+
+void RowScale(Device dev, DType t, Int m, Int n, void* A, Int lda, const void* sig, Int i0, Int is, hipStream_t s) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+    if (m <= 0 || n <= 0) return;
+    if (dev == Device::GPU) {
+        check(kern::row_scale((int)t, m, n, A, lda, sig, i0, is, s), "row_scale");
+        return;
+    }
+    if (t == DType::F64) cpu_row_scale(m, n, static_cast<double*>(A), lda, static_cast<const double*>(sig), i0, is);
+    else cpu_row_scale(m, n, static_cast<float*>(A), lda, static_cast<const float*>(sig), i0, is);
+}
+
 // triang_inv::LVar3Unb (Inverse/Triangular/LVar3.hpp:17-43) on the stored
 // triangle: S(i,j), i >= j, is A(i,j) when lower and A(j,i) when upper (UVar3Unb
 // is the same loop on the transpose).  Divides without a singularity test.

@@ -64,6 +64,25 @@ void LU(Device dev, DType t, Int m, Int w, void* A, Int lda, int* piv, int row_o
 // the opposite order); bit-exact.  info (may be null): non-zero makes it a no-op
 void Laswp(Device dev, DType t, Int m, Int n, void* A, Int lda, const int* piv, Int k0, Int k1, Int voff, bool inverse,
            const int* info, hipStream_t s);
+// A = Q R of the m x w column panel A in place, w <= kern::kGeqrfLeafCols, any m
+// (qr::PanelHouseholder with reflector::Col): R with a non-negative diagonal in
+// the upper trapezoid, the reflectors u_j (implicit leading 1) below it, tau[j]
+// the Householder scalars and sig[j] = +-1 the signature, k = min(m, w) of each
+// in the matrix's type; Q = H_0 .. H_{k-1} diag(sig), H_j = I - tau_j [1; u_j]
+// [1; u_j]^T.  A column that is zero below the diagonal gets tau = 2.  Norms and
+// dots are scaled by the column's largest magnitude, so no stored range
+// overflows; the reference's rescue loop for subnormal columns is left out.  NaN
+// and Inf propagate.  tau, sig and work (QRWorkBytes(dev, m) bytes) live in the
+// matrix's memory space.  On the GPU this is launches and nothing else.  f64/f32
+size_t QRWorkBytes(Device dev, Int m);
+void QR(Device dev, DType t, Int m, Int w, void* A, Int lda, void* tau, void* sig, void* work, hipStream_t s);
+// U (m x nb) := the reflectors packed below A's diagonal, made explicit (zero
+// above the diagonal, 1 on it)
+void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s);
+// S (nb x nb) := tril(S) with diag(S) = 1 / tau (FixDiagonal, ApplyPacked/LLVF.hpp)
+void QRFixT(Device dev, DType t, Int nb, void* S, Int lds, const void* tau, hipStream_t s);
+// A(i, :) *= sig[i0 + i * is] (DiagonalScale(LEFT) by a vector of A's type and memory space)
+void RowScale(Device dev, DType t, Int m, Int n, void* A, Int lda, const void* sig, Int i0, Int is, hipStream_t s);
 // A := tri(A)^-1 in place on the uplo triangle of the n x n A (unit: the
 // diagonal is neither read nor written), n <= kern::kTrtriMax on the GPU
 // (triang_inv::LVar3Unb / UVar3Unb).  No singularity test.  f64/f32

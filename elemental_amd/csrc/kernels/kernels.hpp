@@ -355,5 +355,22 @@ hipError_t perm_meta(const int* piv, i64 k0, i64 nbr, i64 m, int stride, int ali
 hipError_t perm_move(size_t elem_size, bool scatter, const int* piv, const int* meta, i64 k0, i64 nbr, int stride,
                      int rank, void* A, i64 lda, i64 lw, void* buf, hipStream_t s);
 hipError_t perm_apply(size_t elem_size, const int* meta, i64 nbr, bool inverse, void* gathered, i64 lw, hipStream_t s);
+// Householder QR of one m x w column panel in place (geqrf.hip), w <=
+// kGeqrfLeafCols, any m: kGeqrfLeafRows rows per workgroup, one launch per column
+// step (min(m, w) + 1 launches, nothing else on the host, nothing read back).
+// On return the upper trapezoid holds R with a non-negative diagonal, the strict
+// lower part the reflector vectors (implicit leading 1), tau[0..k) the Householder
+// scalars and sig[0..k) the signature (+-1), both of the matrix's type; Q = H_0 ..
+// H_{k-1} diag(sig).  work: geqrf_work_bytes(m) bytes of device scratch.  f64 / f32.
+constexpr int kGeqrfLeafCols = 16, kGeqrfLeafRows = 256;
+size_t geqrf_work_bytes(i64 m);
+hipError_t geqrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, void* tau, void* sig, void* work, hipStream_t s);
+// U (m x nb) := the reflectors packed below the diagonal of A, explicit: zero
+// above the diagonal and 1 on it
+hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s);
+// S (nb x nb) := tril(S) with diag(S) = 1 / tau (FixDiagonal of the UT transform)
+hipError_t qr_fix_t(int dtype, i64 nb, void* S, i64 lds, const void* tau, hipStream_t s);
+// A(i, :) *= sig[i0 + i * is] for the m x n A; sig has the matrix's type
+hipError_t row_scale(int dtype, i64 m, i64 n, void* A, i64 lda, const void* sig, i64 i0, i64 is, hipStream_t s);
 }  // namespace kern
 }  // namespace elx

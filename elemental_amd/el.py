@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "QR", "QRApplyQ", "QRSolveAfter", "QRExplicit", "QRExplicitTriang", "LeastSquares", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -471,6 +471,46 @@ def LinearSolve(A: DistMatrix, B: DistMatrix):
     """El::LinearSolve(A, B) (src/lapack_like/solve/Linear.cpp): B := A^-1 B; A is
     factored in a copy and left as it was."""
     call("elx_linear_solve", A.h, B.h)
+
+
+def QR(A: DistMatrix):
+    """El::QR(A, householderScalars, signature) (factor/QR/Householder.hpp): A is
+    overwritten with R (upper trapezoid, non-negative diagonal) and the Householder
+    reflectors below it; returns (t, d), [*,*] matrices of min(m, n) x 1: the
+    Householder scalars and the signature (+-1), Q = H_0 .. H_{k-1} diag(d)."""
+    t, d = A.like(STAR, STAR), A.like(STAR, STAR)
+    call("elx_qr", A.h, t.h, d.h)
+    return t, d
+
+
+def QRApplyQ(side, orientation, A: DistMatrix, t: DistMatrix, d: DistMatrix, B: DistMatrix):
+    """El::qr::ApplyQ(side, orientation, A, t, d, B): B := Q B (NORMAL) or Q^T B
+    (TRANSPOSE / ADJOINT) from what El::QR left in A, t and d.  LEFT only."""
+    call("elx_qr_apply_q", side, orientation, A.h, t.h, d.h, B.h)
+
+
+def QRSolveAfter(orientation, A: DistMatrix, t: DistMatrix, d: DistMatrix, B: DistMatrix, X: DistMatrix):
+    """El::qr::SolveAfter(orientation, A, t, d, B, X), m >= n: NORMAL the
+    least-squares X = R^-1 (Q^T B)(0:n, :), TRANSPOSE / ADJOINT the minimum-norm X
+    with A^T X = B."""
+    call("elx_qr_solve_after", orientation, A.h, t.h, d.h, B.h, X.h)
+
+
+def QRExplicit(A: DistMatrix, R: DistMatrix):
+    """El::qr::Explicit(A, R): A := the thin Q (m x k), R := the k x n upper trapezoid."""
+    call("elx_qr_explicit", A.h, R.h)
+
+
+def QRExplicitTriang(A: DistMatrix):
+    """El::qr::ExplicitTriang(A): A := R, the k x n upper trapezoid."""
+    call("elx_qr_explicit_triang", A.h)
+
+
+def LeastSquares(orientation, A: DistMatrix, B: DistMatrix, X: DistMatrix):
+    """El::LeastSquares(orientation, A, B, X) for m >= n: X := argmin ||A X - B||_F
+    (NORMAL) or the minimum-norm solution of A^T X = B; A is factored in a copy.
+    m < n raises UnsupportedError."""
+    call("elx_least_squares", orientation, A.h, B.h, X.h)
 
 
 def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, conjugate: bool = False):

@@ -1173,6 +1173,63 @@ template <typename T>
 void LinearSolve(const AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& B) {
     detail::Check(elx_linear_solve(A.h(), B.h()));
 }
+// Householder QR (src/lapack_like/factor/QR/Householder.hpp): A = Q R in place.  The
+// upper trapezoid receives R with a non-negative diagonal, the strict lower part
+// the reflectors u_j (implicit leading 1); householderScalars and signature are
+// resized to min(m, n) x 1: Q = H_0 .. H_{k-1} diag(signature), H_j = I -
+// householderScalars_j [1; u_j][1; u_j]^T.  float and double.  A Matrix runs the
+// local driver on its buffer, on A's stream, without synchronizing
+template <typename T>
+void QR(AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& householderScalars, AbstractDistMatrix<T>& signature) {
+    detail::Check(elx_qr(A.h(), householderScalars.h(), signature.h()));
+}
+template <typename T>
+void QR(AbstractMatrix<T>& A, AbstractMatrix<T>& householderScalars, AbstractMatrix<T>& signature) {
+    if (householderScalars.GetDevice() != A.GetDevice() || signature.GetDevice() != A.GetDevice())
+        throw LogicError("QR: A, householderScalars and signature must be on the same device");
+    const Int k = A.Height() < A.Width() ? A.Height() : A.Width();
+    householderScalars.Resize(k, 1);
+    signature.Resize(k, 1);
+    detail::Check(elx_matrix_qr(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), A.Height(), A.Width(),
+                                A.Buffer(), A.LDim() > 1 ? A.LDim() : 1, householderScalars.Buffer(),
+                                signature.Buffer(), A.Stream()));
+}
+namespace qr {
+// B := Q B (NORMAL) or Q^H B (ADJOINT / TRANSPOSE) from what QR left (QR/ApplyQ.hpp);
+// side must be LEFT
+template <typename T>
+void ApplyQ(LeftOrRight side, Orientation orientation, const AbstractDistMatrix<T>& A,
+            const AbstractDistMatrix<T>& householderScalars, const AbstractDistMatrix<T>& signature,
+            AbstractDistMatrix<T>& B) {
+    detail::Check(elx_qr_apply_q(side, orientation, A.h(), householderScalars.h(), signature.h(), B.h()));
+}
+// NORMAL: X := argmin ||A X - B||_F; ADJOINT / TRANSPOSE: the minimum-norm X with
+// A^H X = B (QR/SolveAfter.hpp).  A must have at least as many rows as columns
+template <typename T>
+void SolveAfter(Orientation orientation, const AbstractDistMatrix<T>& A,
+                const AbstractDistMatrix<T>& householderScalars, const AbstractDistMatrix<T>& signature,
+                const AbstractDistMatrix<T>& B, AbstractDistMatrix<T>& X) {
+    detail::Check(elx_qr_solve_after(orientation, A.h(), householderScalars.h(), signature.h(), B.h(), X.h()));
+}
+// A := the thin Q, R := the upper trapezoid (QR/Explicit.hpp)
+template <typename T>
+void Explicit(AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& R) {
+    detail::Check(elx_qr_explicit(A.h(), R.h()));
+}
+// A := R
+template <typename T>
+void ExplicitTriang(AbstractDistMatrix<T>& A) {
+    detail::Check(elx_qr_explicit_triang(A.h()));
+}
+}  // namespace qr
+// X := the least-squares (NORMAL) or minimum-norm (ADJOINT / TRANSPOSE) solution; A
+// (m >= n; m < n throws UnsupportedError) is factored in a copy
+// (src/lapack_like/euclidean_min/LeastSquares.cpp)
+template <typename T>
+void LeastSquares(Orientation orientation, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& B,
+                  AbstractDistMatrix<T>& X) {
+    detail::Check(elx_least_squares(orientation, A.h(), B.h(), X.h()));
+}
 // TriangularInverse (src/lapack_like/funcs/Inverse/Triangular.cpp): A := tri(A)^-1 in
 // place on the uplo triangle; the other triangle, and with UNIT the diagonal, is
 // neither read nor written.  No singularity test: an exact zero on a NON_UNIT

@@ -230,6 +230,15 @@ int elx_matrix_hpd_inverse(int dtype, int device, int uplo, int64_t n, void* A, 
  * pivot is exactly zero (A and piv are then unspecified).  Synchronizes the stream
  * (the status has to be read back).  f32/f64. */
 int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, int32_t* piv, void* stream);
+/* El::QR on Matrix<T> (src/lapack_like/factor/QR/Householder.hpp): A = Q R of the m x n
+ * A in place by Householder reflections.  On return the upper trapezoid holds R with a
+ * non-negative diagonal and the strict lower part the reflectors u_j (implicit leading
+ * 1); tau and sig receive min(m, n) entries of the matrix's type in its memory space:
+ * the Householder scalars and the signature (+-1), Q = H_0 .. H_{k-1} diag(sig), H_j =
+ * I - tau_j [1; u_j][1; u_j]^T.  No failure mode; NaN and Inf propagate.  Does NOT
+ * synchronize: on the GPU it is launches on the stream and nothing else.  f32/f64. */
+int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, void* tau, void* sig,
+                  void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -563,6 +572,26 @@ int elx_linear_solve(elx_dm_t A, elx_dm_t B);
 /* the leaf kernel's panel width and its rows per workgroup (kGetrfLeafCols, kGetrfLeafRows) */
 int64_t elx_lu_leaf_cols(void);
 int64_t elx_lu_leaf_rows(void);
+/* El::QR (src/lapack_like/factor/QR/Householder.hpp): A = Q R in place; t and d (any
+ * distribution) are resized to min(m, n) x 1 and receive the Householder scalars and
+ * the signature (+-1); R has a non-negative diagonal.  float and double */
+int elx_qr(elx_dm_t A, elx_dm_t t, elx_dm_t d);
+/* El::qr::ApplyQ (QR/ApplyQ.hpp): B := Q B (ELX_NORMAL) or Q^T B from elx_qr's A, t and
+ * d.  side must be ELX_LEFT (ELX_ERR_LOGIC otherwise) */
+int elx_qr_apply_q(int side, int orient, elx_dm_t A, elx_dm_t t, elx_dm_t d, elx_dm_t B);
+/* El::qr::SolveAfter (QR/SolveAfter.hpp), m >= n: ELX_NORMAL X := argmin ||A X - B||_F;
+ * ELX_TRANSPOSE / ELX_ADJOINT the minimum-norm X with A^T X = B */
+int elx_qr_solve_after(int orient, elx_dm_t A, elx_dm_t t, elx_dm_t d, elx_dm_t B, elx_dm_t X);
+/* El::qr::Explicit: A := the thin Q (m x k), R := the k x n upper trapezoid */
+int elx_qr_explicit(elx_dm_t A, elx_dm_t R);
+/* El::qr::ExplicitTriang: A := R */
+int elx_qr_explicit_triang(elx_dm_t A);
+/* El::LeastSquares (src/lapack_like/euclidean_min/LeastSquares.cpp) for m >= n; A is
+ * left as it was.  m < n is ELX_ERR_UNSUPPORTED */
+int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X);
+/* the QR leaf kernel's panel width and its rows per workgroup (kGeqrfLeafCols, kGeqrfLeafRows) */
+int64_t elx_qr_leaf_cols(void);
+int64_t elx_qr_leaf_rows(void);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
