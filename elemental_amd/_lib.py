@@ -204,6 +204,25 @@ _SIGS = {
     "elx_least_squares": (_i, [_i, _vp, _vp, _vp]),
     "elx_qr_leaf_cols": (_i64, []),
     "elx_qr_leaf_rows": (_i64, []),
+    "elx_matrix_gemv": (_i, [_i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),
+    "elx_matrix_ger": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "elx_matrix_symv": (_i, [_i, _i, _i, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),
+    "elx_matrix_symv_accumulate": (_i, [_i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                        _i64, _i64, _i64, _i64, _i64, _vp]),
+    "elx_matrix_syr": (_i, [_i, _i, _i, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
+    "elx_matrix_syr2": (_i, [_i, _i, _i, _i64, _d, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "elx_gemv": (_i, [_i, _d, _vp, _vp, _d, _vp]),
+    "elx_gemv_resize": (_i, [_i, _d, _vp, _vp, _vp]),
+    "elx_local_gemv": (_i, [_i, _d, _vp, _vp, _d, _vp]),
+    "elx_ger": (_i, [_d, _vp, _vp, _vp]),
+    "elx_symv": (_i, [_i, _d, _vp, _vp, _d, _vp, _i]),
+    "elx_symv_local_col_accumulate": (_i, [_i, _d, _vp, _vp, _vp, _vp, _vp, _i]),
+    "elx_syr": (_i, [_i, _d, _vp, _vp, _i]),
+    "elx_syr2": (_i, [_i, _d, _vp, _vp, _vp, _i]),
+    "elx_level2_gemv_rows": (_i64, []),
+    "elx_level2_gemv_cols": (_i64, []),
+    "elx_level2_symv_tile": (_i64, []),
+    "elx_level2_gemv_splits": (_i64, [_i, _i64, _i64]),
     "elx_symm": (_i, [_i, _i, _d, _vp, _vp, _d, _vp, _i]),
     "elx_dm_scale_trapezoid": (_i, [_d, _i, _vp, _i64]),
     "elx_set_blocksize": (_i, [_i64]),

@@ -6,6 +6,7 @@
 #include "core/distmatrix.hpp"
 #include "core/redist.hpp"
 #include "core/gemm.hpp"
+#include "core/level2.hpp"
 #include "core/lu.hpp"
 #include "core/qr.hpp"
 #include "core/random.hpp"
@@ -988,6 +989,144 @@ int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X) {
 }
 int64_t elx_qr_leaf_cols(void) { return kern::kGeqrfLeafCols; }
 int64_t elx_qr_leaf_rows(void) { return kern::kGeqrfLeafRows; }
+// ---- Level 2 ----------------------------------------------------------------------
+namespace {
+void CheckInc(int64_t inc, const char* what) { ELX_REQUIRE(inc >= 1, what, " stride ", inc, " < 1"); }
+void CheckUplo(const char* who, int uplo) {
+    ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, who, ": bad UpperOrLower ", uplo);
+}
+DType RealType(const char* who, int dtype) {
+    const DType t = ToDType(dtype);
+    if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+    return t;
+}
+}  // namespace
+int elx_matrix_gemv(int dtype, int device, int orient, int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
+                    const void* x, int64_t incx, double beta, void* y, int64_t incy, void* stream) {
+    return Guard([&] {
+        CheckOp(orient);
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative Gemv dimension");
+        CheckLd(lda, m, "A");
+        CheckInc(incx, "x");
+        CheckInc(incy, "y");
+        const Device d = ToDevice(device);
+        exec::Gemv(d, ToDType(dtype), orient != ELX_NORMAL, m, n, alpha, A, lda, x, incx, beta, y, incy,
+                   DevStream(d, stream));
+    });
+}
+int elx_matrix_ger(int dtype, int device, int64_t m, int64_t n, double alpha, const void* x, int64_t incx,
+                   const void* y, int64_t incy, void* A, int64_t lda, void* stream) {
+    return Guard([&] {
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative Ger dimension");
+        CheckLd(lda, m, "A");
+        CheckInc(incx, "x");
+        CheckInc(incy, "y");
+        const Device d = ToDevice(device);
+        exec::Ger(d, RealType("Ger", dtype), m, n, alpha, x, incx, y, incy, A, lda, DevStream(d, stream));
+    });
+}
+int elx_matrix_symv(int dtype, int device, int uplo, int64_t n, double alpha, const void* A, int64_t lda, const void* x,
+                    int64_t incx, double beta, void* y, int64_t incy, void* stream) {
+    return Guard([&] {
+        CheckUplo("Symv", uplo);
+        ELX_REQUIRE(n >= 0, "negative Symv dimension");
+        CheckLd(lda, n, "A");
+        CheckInc(incx, "x");
+        CheckInc(incy, "y");
+        const Device d = ToDevice(device);
+        exec::SymvAccumulate(d, RealType("Symv", dtype), uplo == ELX_LOWER, n, n, alpha, A, lda, x, incx, x, incx, beta,
+                             y, incy, nullptr, 1, 0, 1, 0, 1, DevStream(d, stream));
+    });
+}
+int elx_matrix_symv_accumulate(int dtype, int device, int uplo, int64_t m, int64_t n, double alpha, const void* A,
+                               int64_t lda, const void* x_row, int64_t incxr, const void* x_col, int64_t incxc,
+                               void* z_row, int64_t inczr, void* z_col, int64_t inczc, int64_t i0, int64_t istride,
+                               int64_t j0, int64_t jstride, void* stream) {
+    return Guard([&] {
+        CheckUplo("SymvAccumulate", uplo);
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative SymvAccumulate dimension");
+        ELX_REQUIRE(i0 >= 0 && j0 >= 0 && istride >= 1 && jstride >= 1, "SymvAccumulate: bad index map");
+        ELX_REQUIRE(z_row != nullptr && z_col != nullptr, "SymvAccumulate: null output vector");
+        CheckLd(lda, m, "A");
+        CheckInc(incxr, "x_row");
+        CheckInc(incxc, "x_col");
+        CheckInc(inczr, "z_row");
+        CheckInc(inczc, "z_col");
+        const Device d = ToDevice(device);
+        exec::SymvAccumulate(d, RealType("SymvAccumulate", dtype), uplo == ELX_LOWER, m, n, alpha, A, lda, x_row, incxr,
+                             x_col, incxc, 1.0, z_row, inczr, z_col, inczc, i0, istride, j0, jstride,
+                             DevStream(d, stream));
+    });
+}
+int elx_matrix_syr(int dtype, int device, int uplo, int64_t n, double alpha, const void* x, int64_t incx, void* A,
+                   int64_t lda, void* stream) {
+    return Guard([&] {
+        CheckUplo("Syr", uplo);
+        ELX_REQUIRE(n >= 0, "negative Syr dimension");
+        CheckLd(lda, n, "A");
+        CheckInc(incx, "x");
+        const Device d = ToDevice(device);
+        exec::Syr(d, RealType("Syr", dtype), uplo == ELX_LOWER, n, n, alpha, x, incx, x, incx, A, lda, 0, 1, 0, 1,
+                  DevStream(d, stream));
+    });
+}
+int elx_matrix_syr2(int dtype, int device, int uplo, int64_t n, double alpha, const void* x, int64_t incx,
+                    const void* y, int64_t incy, void* A, int64_t lda, void* stream) {
+    return Guard([&] {
+        CheckUplo("Syr2", uplo);
+        ELX_REQUIRE(n >= 0, "negative Syr2 dimension");
+        CheckLd(lda, n, "A");
+        CheckInc(incx, "x");
+        CheckInc(incy, "y");
+        const Device d = ToDevice(device);
+        exec::Syr2(d, RealType("Syr2", dtype), uplo == ELX_LOWER, n, n, alpha, x, incx, x, incx, y, incy, y, incy, A,
+                   lda, 0, 1, 0, 1, DevStream(d, stream));
+    });
+}
+int elx_gemv(int orient, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y) {
+    return Guard([&] {
+        CheckOp(orient);
+        Gemv(orient, alpha, M(A), M(x), beta, M(y));
+    });
+}
+int elx_gemv_resize(int orient, double alpha, elx_dm_t A, elx_dm_t x, elx_dm_t y) {
+    return Guard([&] {
+        CheckOp(orient);
+        GemvResize(orient, alpha, M(A), M(x), M(y));
+    });
+}
+int elx_local_gemv(int orient, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y) {
+    return Guard([&] {
+        CheckOp(orient);
+        LocalGemv(orient, alpha, M(A), M(x), beta, M(y));
+    });
+}
+int elx_ger(double alpha, elx_dm_t x, elx_dm_t y, elx_dm_t A) { return Guard([&] { Ger(alpha, M(x), M(y), M(A)); }); }
+int elx_symv(int uplo, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y, int conjugate) {
+    (void)conjugate;  // real types: Hemv == Symv
+    return Guard([&] { Symv(uplo, alpha, M(A), M(x), beta, M(y)); });
+}
+int elx_symv_local_col_accumulate(int uplo, double alpha, elx_dm_t A, elx_dm_t x_MC_STAR, elx_dm_t x_MR_STAR,
+                                  elx_dm_t z_MC_STAR, elx_dm_t z_MR_STAR, int conjugate) {
+    (void)conjugate;
+    return Guard([&] {
+        symv::LocalColAccumulate(uplo, alpha, M(A), M(x_MC_STAR), M(x_MR_STAR), M(z_MC_STAR), M(z_MR_STAR));
+    });
+}
+int elx_syr(int uplo, double alpha, elx_dm_t x, elx_dm_t A, int conjugate) {
+    (void)conjugate;  // real types: Her == Syr
+    return Guard([&] { Syr(uplo, alpha, M(x), M(A)); });
+}
+int elx_syr2(int uplo, double alpha, elx_dm_t x, elx_dm_t y, elx_dm_t A, int conjugate) {
+    (void)conjugate;  // real types: Her2 == Syr2
+    return Guard([&] { Syr2(uplo, alpha, M(x), M(y), M(A)); });
+}
+int64_t elx_level2_gemv_rows(void) { return kern::kGemvRows; }
+int64_t elx_level2_gemv_cols(void) { return kern::kGemvCols; }
+int64_t elx_level2_symv_tile(void) { return kern::kSymvTile; }
+int64_t elx_level2_gemv_splits(int orient, int64_t m, int64_t n) {
+    return kern::gemv_plan(orient != ELX_NORMAL, m, n).splits;
+}
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C, int conjugate) {
     (void)conjugate;  // real types: Hemm == Symm
     return Guard([&] { Symm(side, uplo, alpha, M(A), M(B), beta, M(C)); });

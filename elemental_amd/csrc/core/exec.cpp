@@ -736,6 +736,157 @@ void FillHash(Device dev, DType t, Int m, Int n, void* A, Int lda, Int i0, Int i
     });
 }
 
+namespace {
+void RequireReal(DType t, const char* who) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+}
+template <typename S>
+void cpu_vec_scale(Int len, double beta, S* y, Int incy) {
+    using Cm = typename H<S>::C;
+    if (beta == 1.0) return;
+    for (Int i = 0; i < len; ++i) H<S>::st(y + i * incy, beta == 0.0 ? Cm(0) : (Cm)beta * H<S>::ld(y + i * incy));
+}
+template <typename S>
+void cpu_finish(S* y, double alpha, typename H<S>::C acc, double beta) {
+    using Cm = typename H<S>::C;
+    H<S>::st(y, beta == 0.0 ? (Cm)alpha * acc : (Cm)alpha * acc + (Cm)beta * H<S>::ld(y));
+}
+template <typename S>
+void cpu_gemv(bool trans, Int m, Int n, double alpha, const S* A, Int lda, const S* x, Int incx, double beta, S* y,
+              Int incy) {
+    using Cm = typename H<S>::C;
+    if (trans) {
+        for (Int j = 0; j < n; ++j) {
+            Cm acc = Cm(0);
+            for (Int i = 0; i < m; ++i) acc += H<S>::ld(A + i + j * lda) * H<S>::ld(x + i * incx);
+            cpu_finish(y + j * incy, alpha, acc, beta);
+        }
+        return;
+    }
+    std::vector<Cm> acc(static_cast<size_t>(m), Cm(0));
+    for (Int j = 0; j < n; ++j) {
+        const Cm xv = H<S>::ld(x + j * incx);
+        for (Int i = 0; i < m; ++i) acc[i] += H<S>::ld(A + i + j * lda) * xv;
+    }
+    for (Int i = 0; i < m; ++i) cpu_finish(y + i * incy, alpha, acc[i], beta);
+}
+struct HostTri {
+    bool lower;
+    Int i0, is, j0, js;
+    bool in(Int i, Int j) const { return lower ? i0 + i * is >= j0 + j * js : i0 + i * is <= j0 + j * js; }
+    bool strict(Int i, Int j) const { return lower ? i0 + i * is > j0 + j * js : i0 + i * is < j0 + j * js; }
+};
+template <typename S>
+void cpu_symv(const HostTri& tri, Int m, Int n, double alpha, const S* A, Int lda, const S* xr, Int incxr, const S* xc,
+              Int incxc, double beta, S* zr, Int inczr, S* zc, Int inczc) {
+    using Cm = typename H<S>::C;
+    std::vector<Cm> ar(static_cast<size_t>(m), Cm(0)), ac(static_cast<size_t>(n), Cm(0));
+    for (Int j = 0; j < n; ++j) {
+        const Cm xv = H<S>::ld(xc + j * incxc);
+        for (Int i = 0; i < m; ++i) {
+            if (!tri.in(i, j)) continue;
+            const Cm a = H<S>::ld(A + i + j * lda);
+            ar[i] += a * xv;
+            if (tri.strict(i, j)) ac[j] += a * H<S>::ld(xr + i * incxr);
+        }
+    }
+    if (zc) {
+        for (Int i = 0; i < m; ++i) cpu_finish(zr + i * inczr, alpha, ar[i], beta);
+        for (Int j = 0; j < n; ++j) cpu_finish(zc + j * inczc, alpha, ac[j], beta);
+    } else {
+        for (Int i = 0; i < m; ++i) cpu_finish(zr + i * inczr, alpha, ar[i] + ac[i], beta);
+    }
+}
+// terms 0: Ger (no triangle), 1: Syr, 2: Syr2
+template <typename S>
+void cpu_rank_update(int terms, const HostTri& tri, Int m, Int n, double alpha, const S* xr, Int incxr, const S* yc,
+                     Int incyc, const S* yr, Int incyr, const S* xc, Int incxc, S* A, Int lda) {
+    using Cm = typename H<S>::C;
+    for (Int j = 0; j < n; ++j) {
+        const Cm sv = H<S>::ld(yc + j * incyc), tv = terms == 2 ? H<S>::ld(xc + j * incxc) : Cm(0);
+        for (Int i = 0; i < m; ++i) {
+            if (terms != 0 && !tri.in(i, j)) continue;
+            Cm z = H<S>::ld(A + i + j * lda) + ((Cm)alpha * H<S>::ld(xr + i * incxr)) * sv;
+            if (terms == 2) z += ((Cm)alpha * H<S>::ld(yr + i * incyr)) * tv;
+            H<S>::st(A + i + j * lda, z);
+        }
+    }
+}
+void RankUpdate(const char* who, Device dev, DType t, int terms, bool lower, Int m, Int n, double alpha, const void* xr,
+                Int incxr, const void* yc, Int incyc, const void* yr, Int incyr, const void* xc, Int incxc, void* A,
+                Int lda, Int i0, Int is, Int j0, Int js, hipStream_t s) {
+    RequireReal(t, who);
+    if (m <= 0 || n <= 0 || alpha == 0.0) return;
+    if (dev == Device::GPU) {
+        check(kern::rank_update((int)t, terms, lower, m, n, alpha, xr, incxr, yc, incyc, yr, incyr, xc, incxc, A, lda,
+                                i0, is, j0, js, s),
+              who);
+        return;
+    }
+    const HostTri tri{lower, i0, is, j0, js};
+    HOST_DTYPE_SWITCH(t, S,
+                      cpu_rank_update<S>(terms, tri, m, n, alpha, static_cast<const S*>(xr), incxr,
+                                         static_cast<const S*>(yc), incyc, static_cast<const S*>(yr), incyr,
+                                         static_cast<const S*>(xc), incxc, static_cast<S*>(A), lda));
+}
+}  // namespace
+
+void Gemv(Device dev, DType t, bool trans, Int m, Int n, double alpha, const void* A, Int lda, const void* x, Int incx,
+          double beta, void* y, Int incy, hipStream_t s) {
+    const Int ylen = trans ? n : m, xlen = trans ? m : n;
+    if (ylen <= 0) return;
+    if (dev == Device::GPU) {
+        check(kern::gemv((int)t, trans, m, n, alpha, A, lda, x, incx, beta, y, incy, s), "gemv");
+        return;
+    }
+    HOST_DTYPE_SWITCH(t, S, {
+        if (xlen <= 0 || alpha == 0.0) cpu_vec_scale<S>(ylen, beta, static_cast<S*>(y), incy);
+        else cpu_gemv<S>(trans, m, n, alpha, static_cast<const S*>(A), lda, static_cast<const S*>(x), incx, beta,
+                         static_cast<S*>(y), incy);
+    });
+}
+
+void Ger(Device dev, DType t, Int m, Int n, double alpha, const void* x, Int incx, const void* y, Int incy, void* A,
+         Int lda, hipStream_t s) {
+    RankUpdate("Ger", dev, t, 0, true, m, n, alpha, x, incx, y, incy, nullptr, 1, nullptr, 1, A, lda, 0, 1, 0, 1, s);
+}
+
+void SymvAccumulate(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* A, Int lda,
+                    const void* xr, Int incxr, const void* xc, Int incxc, double beta, void* zr, Int inczr, void* zc,
+                    Int inczc, Int i0, Int is, Int j0, Int js, hipStream_t s) {
+    RequireReal(t, "Symv");
+    ELX_REQUIRE(zc != nullptr || m == n, "Symv: one output vector needs a square block, got ", m, " x ", n);
+    if (dev == Device::GPU) {
+        check(kern::symv((int)t, lower, m, n, alpha, A, lda, xr, incxr, xc, incxc, beta, zr, inczr, zc, inczc, i0, is,
+                         j0, js, s),
+              "symv");
+        return;
+    }
+    HOST_DTYPE_SWITCH(t, S, {
+        if (m <= 0 || n <= 0 || alpha == 0.0) {
+            cpu_vec_scale<S>(m, beta, static_cast<S*>(zr), inczr);
+            if (zc) cpu_vec_scale<S>(n, beta, static_cast<S*>(zc), inczc);
+        } else {
+            cpu_symv<S>(HostTri{lower, i0, is, j0, js}, m, n, alpha, static_cast<const S*>(A), lda,
+                        static_cast<const S*>(xr), incxr, static_cast<const S*>(xc), incxc, beta, static_cast<S*>(zr),
+                        inczr, static_cast<S*>(zc), inczc);
+        }
+    });
+}
+
+void Syr(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* xr, Int incxr, const void* xc,
+         Int incxc, void* A, Int lda, Int i0, Int is, Int j0, Int js, hipStream_t s) {
+    RankUpdate("Syr", dev, t, 1, lower, m, n, alpha, xr, incxr, xc, incxc, nullptr, 1, nullptr, 1, A, lda, i0, is, j0,
+               js, s);
+}
+
+void Syr2(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* xr, Int incxr, const void* xc,
+          Int incxc, const void* yr, Int incyr, const void* yc, Int incyc, void* A, Int lda, Int i0, Int is, Int j0,
+          Int js, hipStream_t s) {
+    RankUpdate("Syr2", dev, t, 2, lower, m, n, alpha, xr, incxr, yc, incyc, yr, incyr, xc, incxc, A, lda, i0, is, j0, js,
+               s);
+}
+
 double LoadScalar(DType t, const void* p) {
     double v = 0;
     HOST_DTYPE_SWITCH(t, S, v = (double)H<S>::ld(static_cast<const S*>(p)));

@@ -98,6 +98,33 @@ void TriInverseBatched(DType t, bool lower, bool trans, bool unit, Int nb, Int m
 void ApplyInverse(Device dev, DType t, Int m, Int n, const void* W, Int ldw, void* B, Int ldb, hipStream_t s);
 void FillHash(Device dev, DType t, Int m, Int n, void* A, Int lda, Int i0, Int is, Int j0, Int js,
               uint64_t seed, double center, double radius, hipStream_t s);
+// ---- Level 2 (kernels/level2.hip on the GPU).  Vectors have an element stride
+// >= 1; sums are kept in double (f64) or float (the other types) and rounded once.
+// y := alpha op(A) x + beta y, A m x n (blas::Gemv).  beta == 0: y is not read;
+// alpha == 0 or a zero-length x: y := beta y without reading A or x.  All four types
+void Gemv(Device dev, DType t, bool trans, Int m, Int n, double alpha, const void* A, Int lda, const void* x, Int incx,
+          double beta, void* y, Int incy, hipStream_t s);
+// A += alpha x y^T, A m x n (blas::Geru).  f64/f32
+void Ger(Device dev, DType t, Int m, Int n, double alpha, const void* x, Int incx, const void* y, Int incy, void* A,
+         Int lda, hipStream_t s);
+// symv::LocalColAccumulateL / U on the m x n block whose element (i, j) is global
+// (i0 + i is, j0 + j js), without the reference's copies of the diagonal blocks:
+//   zr[i] := beta zr[i] + alpha sum_{j: gj <= gi} a(i,j) xc[j]     (lower; upper
+//   zc[j] := beta zc[j] + alpha sum_{i: gi >  gj} a(i,j) xr[i]      mirrored)
+// xr, zr are indexed by local row, xc, zc by local column; an element on the
+// other side of the diagonal is never read.  zc null (m == n): both sums go to
+// zr, which with the identity map is blas::Symv.  f64/f32
+void SymvAccumulate(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* A, Int lda,
+                    const void* xr, Int incxr, const void* xc, Int incxc, double beta, void* zr, Int inczr, void* zc,
+                    Int inczc, Int i0, Int is, Int j0, Int js, hipStream_t s);
+// A(i,j) += alpha xr[i] xc[j] on the lower / upper triangle of the same index
+// map; the other triangle is neither read nor written (blas::Syr).  f64/f32
+void Syr(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* xr, Int incxr, const void* xc,
+         Int incxc, void* A, Int lda, Int i0, Int is, Int j0, Int js, hipStream_t s);
+// A(i,j) += alpha (xr[i] yc[j] + yr[i] xc[j]) likewise (blas::Syr2).  f64/f32
+void Syr2(Device dev, DType t, bool lower, Int m, Int n, double alpha, const void* xr, Int incxr, const void* xc,
+          Int incxc, const void* yr, Int incyr, const void* yc, Int incyc, void* A, Int lda, Int i0, Int is, Int j0,
+          Int js, hipStream_t s);
 // host-side scalar conversion of one element (for Get/Set and tests)
 double LoadScalar(DType t, const void* p);
 void StoreScalar(DType t, void* p, double v);

@@ -372,5 +372,46 @@ hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void*
 hipError_t qr_fix_t(int dtype, i64 nb, void* S, i64 lds, const void* tau, hipStream_t s);
 // A(i, :) *= sig[i0 + i * is] for the m x n A; sig has the matrix's type
 hipError_t row_scale(int dtype, i64 m, i64 n, void* A, i64 lda, const void* sig, i64 i0, i64 is, hipStream_t s);
+
+// ---- Level 2 (level2.hip): HBM-bound, no floating-point atomics, bit-reproducible.
+// Column-major A with any lda; vectors with an element stride >= 1.  Sums in
+// double (f64) or float (f32 / f16 / bf16), rounded to the storage type once.
+//   kGemvRows   rows of A per workgroup of gemv_n_kernel, and the row chunk in
+//               which gemv_t_kernel's sum is split
+//   kGemvCols   columns per x chunk of gemv_n_kernel, and the chunk in which its
+//               sum is split
+//   kGemvTCols  columns per workgroup of gemv_t_kernel (one wave each)
+//   kSymvTile   symv_kernel's square tile
+//   kGerRows x kGerCols  the rank updates' tile
+constexpr int kGemvRows = 512, kGemvCols = 256, kGemvTCols = 4, kSymvTile = 128, kGerRows = 512, kGerCols = 32;
+constexpr int kLevel2MaxSplits = 256;
+// How gemv cuts the summed dimension (columns for A x, rows for A^T x) over
+// gridDim.y: `splits` ranges of `per` elements, a multiple of the chunk.  More
+// than one only where the other dimension gives fewer workgroups than the chip
+// has CUs; the partials then go to workspace and level2_reduce_kernel adds them
+// in order.
+struct Level2Plan { int splits; i64 per; };
+Level2Plan gemv_plan(bool trans, i64 m, i64 n);
+// y := alpha op(A) x + beta y, A m x n.  beta == 0: y is not read; alpha == 0 or a
+// zero-length x: A and x are not read.  f64 / f32 / f16 / bf16
+hipError_t gemv(int dtype, bool trans, i64 m, i64 n, double alpha, const void* A, i64 lda, const void* x, i64 incx,
+                double beta, void* y, i64 incy, hipStream_t s);
+// y := beta y (beta == 0: zero, without reading y)
+hipError_t vec_scale(int dtype, i64 len, double beta, void* y, i64 incy, hipStream_t s);
+// The triangle-aware product on the m x n block whose element (i, j) is global
+// (i0 + i is, j0 + j js); with lower (mirrored otherwise) and every element on
+// the other side of the diagonal never read:
+//   zr[i] := beta zr[i] + alpha sum_{j: gj <= gi} a(i,j) xc[j]
+//   zc[j] := beta zc[j] + alpha sum_{i: gi >  gj} a(i,j) xr[i]
+// zc null (m == n): both sums go to zr, which is Symv on a whole matrix.  f64 / f32
+hipError_t symv(int dtype, bool lower, i64 m, i64 n, double alpha, const void* A, i64 lda, const void* xr, i64 incxr,
+                const void* xc, i64 incxc, double beta, void* zr, i64 inczr, void* zc, i64 inczc, i64 i0, i64 is,
+                i64 j0, i64 js, hipStream_t s);
+// A(i,j) += alpha (xr[i] yc[j] [+ yr[i] xc[j]]): terms 0 on the whole block
+// (Ger), 1 (Syr, one product) or 2 (Syr2) on the lower / upper triangle of the
+// index map only; xr, yr are indexed by local row, yc, xc by local column.  f64 / f32
+hipError_t rank_update(int dtype, int terms, bool lower, i64 m, i64 n, double alpha, const void* xr, i64 incxr,
+                       const void* yc, i64 incyc, const void* yr, i64 incyr, const void* xc, i64 incxc, void* A,
+                       i64 lda, i64 i0, i64 is, i64 j0, i64 js, hipStream_t s);
 }  // namespace kern
 }  // namespace elx

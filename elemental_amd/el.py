@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "QR", "QRApplyQ", "QRSolveAfter", "QRExplicit", "QRExplicitTriang", "LeastSquares", "Symm", "Hemm", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "QR", "QRApplyQ", "QRSolveAfter", "QRExplicit", "QRExplicitTriang", "LeastSquares", "Symm", "Hemm", "Gemv", "LocalGemv", "Ger", "Symv", "Hemv", "SymvLocalColAccumulate", "Syr", "Syr2", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -521,6 +521,57 @@ def Symm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix, c
 def Hemm(side, uplo, alpha, A: DistMatrix, B: DistMatrix, beta, C: DistMatrix):
     """El::Hemm: Symm with conjugation, identical for the real types."""
     Symm(side, uplo, alpha, A, B, beta, C, conjugate=True)
+
+
+def Gemv(orientation, alpha, A: DistMatrix, x: DistMatrix, beta, y: DistMatrix):
+    """El::Gemv(orientation, alpha, A, x, beta, y) (Gemv/Normal.hpp, Gemv/Transpose.hpp):
+    y := alpha op(A) x + beta y; x and y are n x 1 or 1 x n matrices of any distribution.
+    beta=None is the beta-less overload: y is aligned with A, resized to a column vector
+    and zeroed first."""
+    if beta is None:
+        call("elx_gemv_resize", orientation, float(alpha), A.h, x.h, y.h)
+    else:
+        call("elx_gemv", orientation, float(alpha), A.h, x.h, float(beta), y.h)
+
+
+def LocalGemv(orientation, alpha, A: DistMatrix, x: DistMatrix, beta, y: DistMatrix):
+    """El::LocalGemv: the local product on vectors already spread over and aligned with
+    the matching dimension of A [MC,MR] (NORMAL: x [MR,*] or [*,MR], y [MC,*] or [*,MC])."""
+    call("elx_local_gemv", orientation, float(alpha), A.h, x.h, float(beta), y.h)
+
+
+def Ger(alpha, x: DistMatrix, y: DistMatrix, A: DistMatrix):
+    """El::Ger(alpha, x, y, A) (Ger.cpp): A += alpha x y^T."""
+    call("elx_ger", float(alpha), x.h, y.h, A.h)
+
+
+def Symv(uplo, alpha, A: DistMatrix, x: DistMatrix, beta, y: DistMatrix, conjugate: bool = False):
+    """El::Symv(uplo, alpha, A, x, beta, y) (Symv.cpp): y := alpha A x + beta y with the
+    symmetric A given by its uplo triangle; the other triangle is never read."""
+    call("elx_symv", uplo, float(alpha), A.h, x.h, float(beta), y.h, int(bool(conjugate)))
+
+
+def Hemv(uplo, alpha, A: DistMatrix, x: DistMatrix, beta, y: DistMatrix):
+    """El::Hemv: Symv with conjugation, identical for the real types."""
+    Symv(uplo, alpha, A, x, beta, y, conjugate=True)
+
+
+def SymvLocalColAccumulate(uplo, alpha, A: DistMatrix, x_MC_STAR: DistMatrix, x_MR_STAR: DistMatrix,
+                           z_MC_STAR: DistMatrix, z_MR_STAR: DistMatrix, conjugate: bool = False):
+    """El::symv::LocalColAccumulate (Symv/L.hpp, Symv/U.hpp) on A's local block:
+    z[MC,*] += alpha tri(A) x[MR,*], z[MR,*] += alpha tri'(A)^T x[MC,*]."""
+    call("elx_symv_local_col_accumulate", uplo, float(alpha), A.h, x_MC_STAR.h, x_MR_STAR.h, z_MC_STAR.h,
+         z_MR_STAR.h, int(bool(conjugate)))
+
+
+def Syr(uplo, alpha, x: DistMatrix, A: DistMatrix, conjugate: bool = False):
+    """El::Syr(uplo, alpha, x, A) (Syr.cpp): A += alpha x x^T on the uplo triangle."""
+    call("elx_syr", uplo, float(alpha), x.h, A.h, int(bool(conjugate)))
+
+
+def Syr2(uplo, alpha, x: DistMatrix, y: DistMatrix, A: DistMatrix, conjugate: bool = False):
+    """El::Syr2(uplo, alpha, x, y, A) (Syr2.cpp): A += alpha (x y^T + y x^T) on the uplo triangle."""
+    call("elx_syr2", uplo, float(alpha), x.h, y.h, A.h, int(bool(conjugate)))
 
 
 def ScaleTrapezoid(alpha, uplo, A: DistMatrix, offset: int = 0):

@@ -1296,6 +1296,211 @@ void LocalHPDInverse(UpperOrLower uplo, DistMatrix<T, STAR, STAR, ELEMENT, D>& A
     detail::Check(elx_matrix_hpd_inverse(detail::TypeCode<T>::value, static_cast<int>(D), uplo, A.Height(), A.Buffer(),
                                          A.LDim() > 1 ? A.LDim() : 1, A.Stream()));
 }
+// ---- Level 2 (include/El/blas_like/level2.hpp) -----------------------------------------
+// A vector is an n x 1 or a 1 x n matrix.  On local matrices the HBM-bound kernels run on
+// the GPU (on the output's stream), the library's host loops on the CPU.  Real types:
+// Hemv = Symv, Her = Syr, Her2 = Syr2, Geru = Ger, and `conjugate` changes nothing.
+// Gemv takes all four element types, the others float and double.
+namespace detail {
+template <typename T> bool IsVec(const AbstractMatrix<T>& v) {
+    return v.Height() == 1 || v.Width() == 1 || v.Height() == 0 || v.Width() == 0;
+}
+template <typename T> Int VecLen(const AbstractMatrix<T>& v) {
+    return v.Width() == 1 ? v.Height() : v.Height() == 1 ? v.Width() : 0;
+}
+template <typename T> Int VecInc(const AbstractMatrix<T>& v) { return v.Width() == 1 || v.Height() != 1 ? 1 : v.LDim(); }
+template <typename M> std::string Dims(const char* name, const M& A) {
+    return std::string(name) + " ~ " + std::to_string(A.Height()) + " x " + std::to_string(A.Width());
+}
+}  // namespace detail
+// Gemv (Gemv.cpp): y := alpha op(A) x + beta y
+template <typename T>
+void Gemv(Orientation orientation, T alpha, const AbstractMatrix<T>& A, const AbstractMatrix<T>& x, T beta,
+          AbstractMatrix<T>& y) {
+    if (A.GetDevice() != y.GetDevice() || x.GetDevice() != y.GetDevice())
+        throw LogicError("Gemv: A, x and y must be on the same device");
+    const Int ylen = orientation == NORMAL ? A.Height() : A.Width(), xlen = orientation == NORMAL ? A.Width() : A.Height();
+    if (!detail::IsVec(x) || !detail::IsVec(y) || detail::VecLen(x) != xlen || detail::VecLen(y) != ylen)
+        throw LogicError("Nonconformal Gemv: " + detail::Dims("A", A) + ", " + detail::Dims("x", x) + ", " +
+                         detail::Dims("y", y));
+    detail::LocalFence<T> fence(y, {&A, &x});
+    detail::Check(elx_matrix_gemv(detail::TypeCode<T>::value, static_cast<int>(y.GetDevice()), orientation, A.Height(),
+                                  A.Width(), detail::ToDouble(alpha), A.LockedBuffer(), A.LDim(), x.LockedBuffer(),
+                                  detail::VecInc(x), detail::ToDouble(beta), y.Buffer(), detail::VecInc(y), y.Stream()));
+}
+// beta-less form: y resized to a column vector and overwritten
+template <typename T>
+void Gemv(Orientation orientation, T alpha, const AbstractMatrix<T>& A, const AbstractMatrix<T>& x,
+          AbstractMatrix<T>& y) {
+    y.Resize(orientation == NORMAL ? A.Height() : A.Width(), 1);
+    Gemv(orientation, alpha, A, x, detail::FromDouble<T>(0.0), y);
+}
+template <typename T, Device D>
+void Gemv(Orientation orientation, T alpha, const Matrix<T, D>& A, const Matrix<T, D>& x, T beta, Matrix<T, D>& y) {
+    Gemv(orientation, alpha, static_cast<const AbstractMatrix<T>&>(A), static_cast<const AbstractMatrix<T>&>(x), beta,
+         static_cast<AbstractMatrix<T>&>(y));
+}
+template <typename T, Device D>
+void Gemv(Orientation orientation, T alpha, const Matrix<T, D>& A, const Matrix<T, D>& x, Matrix<T, D>& y) {
+    Gemv(orientation, alpha, static_cast<const AbstractMatrix<T>&>(A), static_cast<const AbstractMatrix<T>&>(x),
+         static_cast<AbstractMatrix<T>&>(y));
+}
+// on DistMatrices (Gemv/Normal.hpp, Gemv/Transpose.hpp)
+template <typename T>
+void Gemv(Orientation orientation, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& x, T beta,
+          AbstractDistMatrix<T>& y) {
+    detail::Check(elx_gemv(orientation, detail::ToDouble(alpha), A.h(), x.h(), detail::ToDouble(beta), y.h()));
+}
+// beta-less form: y is aligned with A, resized to a column vector and zeroed first
+template <typename T>
+void Gemv(Orientation orientation, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& x,
+          AbstractDistMatrix<T>& y) {
+    detail::Check(elx_gemv_resize(orientation, detail::ToDouble(alpha), A.h(), x.h(), y.h()));
+}
+// the local product on operands already spread and aligned with A [MC,MR]
+template <typename T>
+void LocalGemv(Orientation orientation, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& x, T beta,
+               AbstractDistMatrix<T>& y) {
+    detail::Check(elx_local_gemv(orientation, detail::ToDouble(alpha), A.h(), x.h(), detail::ToDouble(beta), y.h()));
+}
+// Ger / Geru (Ger.cpp): A += alpha x y^T
+template <typename T>
+void Ger(T alpha, const AbstractMatrix<T>& x, const AbstractMatrix<T>& y, AbstractMatrix<T>& A) {
+    if (x.GetDevice() != A.GetDevice() || y.GetDevice() != A.GetDevice())
+        throw LogicError("Ger: x, y and A must be on the same device");
+    if (!detail::IsVec(x) || !detail::IsVec(y) || detail::VecLen(x) != A.Height() || detail::VecLen(y) != A.Width())
+        throw LogicError("Nonconformal Ger: " + detail::Dims("A", A) + ", " + detail::Dims("x", x) + ", " +
+                         detail::Dims("y", y));
+    detail::LocalFence<T> fence(A, {&x, &y});
+    detail::Check(elx_matrix_ger(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), A.Height(), A.Width(),
+                                 detail::ToDouble(alpha), x.LockedBuffer(), detail::VecInc(x), y.LockedBuffer(),
+                                 detail::VecInc(y), A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void Ger(T alpha, const Matrix<T, D>& x, const Matrix<T, D>& y, Matrix<T, D>& A) {
+    Ger(alpha, static_cast<const AbstractMatrix<T>&>(x), static_cast<const AbstractMatrix<T>&>(y),
+        static_cast<AbstractMatrix<T>&>(A));
+}
+template <typename T>
+void Ger(T alpha, const AbstractDistMatrix<T>& x, const AbstractDistMatrix<T>& y, AbstractDistMatrix<T>& A) {
+    detail::Check(elx_ger(detail::ToDouble(alpha), x.h(), y.h(), A.h()));
+}
+template <typename T, Device D>
+void Geru(T alpha, const Matrix<T, D>& x, const Matrix<T, D>& y, Matrix<T, D>& A) { Ger(alpha, x, y, A); }
+template <typename T>
+void Geru(T alpha, const AbstractDistMatrix<T>& x, const AbstractDistMatrix<T>& y, AbstractDistMatrix<T>& A) {
+    Ger(alpha, x, y, A);
+}
+// Symv / Hemv (Symv.cpp): y := alpha A x + beta y, A symmetric; only its uplo triangle is read
+template <typename T>
+void Symv(UpperOrLower uplo, T alpha, const AbstractMatrix<T>& A, const AbstractMatrix<T>& x, T beta,
+          AbstractMatrix<T>& y, bool /*conjugate*/ = false) {
+    if (A.GetDevice() != y.GetDevice() || x.GetDevice() != y.GetDevice())
+        throw LogicError("Symv: A, x and y must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("A must be square: " + detail::Dims("A", A));
+    if (!detail::IsVec(x) || !detail::IsVec(y) || detail::VecLen(x) != A.Height() || detail::VecLen(y) != A.Height())
+        throw LogicError("Nonconformal Symv: " + detail::Dims("A", A) + ", " + detail::Dims("x", x) + ", " +
+                         detail::Dims("y", y));
+    detail::LocalFence<T> fence(y, {&A, &x});
+    detail::Check(elx_matrix_symv(detail::TypeCode<T>::value, static_cast<int>(y.GetDevice()), uplo, A.Height(),
+                                  detail::ToDouble(alpha), A.LockedBuffer(), A.LDim(), x.LockedBuffer(),
+                                  detail::VecInc(x), detail::ToDouble(beta), y.Buffer(), detail::VecInc(y), y.Stream()));
+}
+template <typename T, Device D>
+void Symv(UpperOrLower uplo, T alpha, const Matrix<T, D>& A, const Matrix<T, D>& x, T beta, Matrix<T, D>& y,
+          bool conjugate = false) {
+    Symv(uplo, alpha, static_cast<const AbstractMatrix<T>&>(A), static_cast<const AbstractMatrix<T>&>(x), beta,
+         static_cast<AbstractMatrix<T>&>(y), conjugate);
+}
+template <typename T>
+void Symv(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& x, T beta,
+          AbstractDistMatrix<T>& y, bool conjugate = false) {
+    detail::Check(elx_symv(uplo, detail::ToDouble(alpha), A.h(), x.h(), detail::ToDouble(beta), y.h(), conjugate));
+}
+template <typename T, Device D>
+void Hemv(UpperOrLower uplo, T alpha, const Matrix<T, D>& A, const Matrix<T, D>& x, T beta, Matrix<T, D>& y) {
+    Symv(uplo, alpha, A, x, beta, y, true);
+}
+template <typename T>
+void Hemv(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& x, T beta,
+          AbstractDistMatrix<T>& y) {
+    Symv(uplo, alpha, A, x, beta, y, true);
+}
+namespace symv {
+// z[MC,*] += alpha tri(A) x[MR,*] and z[MR,*] += alpha tri'(A)^T x[MC,*] on A's local block
+// (Symv/L.hpp, Symv/U.hpp), the reference's signature without its SymvCtrl
+template <typename T, Device D>
+void LocalColAccumulate(UpperOrLower uplo, T alpha, const DistMatrix<T, MC, MR, ELEMENT, D>& A,
+                        const DistMatrix<T, MC, STAR, ELEMENT, D>& x_MC_STAR,
+                        const DistMatrix<T, MR, STAR, ELEMENT, D>& x_MR_STAR,
+                        DistMatrix<T, MC, STAR, ELEMENT, D>& z_MC_STAR, DistMatrix<T, MR, STAR, ELEMENT, D>& z_MR_STAR,
+                        bool conjugate = false) {
+    detail::Check(elx_symv_local_col_accumulate(uplo, detail::ToDouble(alpha), A.h(), x_MC_STAR.h(), x_MR_STAR.h(),
+                                                z_MC_STAR.h(), z_MR_STAR.h(), conjugate));
+}
+}  // namespace symv
+// Syr / Her (Syr.cpp): A += alpha x x^T on the uplo triangle; the other triangle is
+// neither read nor written
+template <typename T>
+void Syr(UpperOrLower uplo, T alpha, const AbstractMatrix<T>& x, AbstractMatrix<T>& A, bool /*conjugate*/ = false) {
+    if (x.GetDevice() != A.GetDevice()) throw LogicError("Syr: x and A must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("A must be square: " + detail::Dims("A", A));
+    if (!detail::IsVec(x) || detail::VecLen(x) != A.Height())
+        throw LogicError("Nonconformal Syr: " + detail::Dims("A", A) + ", " + detail::Dims("x", x));
+    detail::LocalFence<T> fence(A, {&x});
+    detail::Check(elx_matrix_syr(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, A.Height(),
+                                 detail::ToDouble(alpha), x.LockedBuffer(), detail::VecInc(x), A.Buffer(), A.LDim(),
+                                 A.Stream()));
+}
+template <typename T, Device D>
+void Syr(UpperOrLower uplo, T alpha, const Matrix<T, D>& x, Matrix<T, D>& A, bool conjugate = false) {
+    Syr(uplo, alpha, static_cast<const AbstractMatrix<T>&>(x), static_cast<AbstractMatrix<T>&>(A), conjugate);
+}
+template <typename T>
+void Syr(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& x, AbstractDistMatrix<T>& A, bool conjugate = false) {
+    detail::Check(elx_syr(uplo, detail::ToDouble(alpha), x.h(), A.h(), conjugate));
+}
+template <typename T, Device D>
+void Her(UpperOrLower uplo, T alpha, const Matrix<T, D>& x, Matrix<T, D>& A) { Syr(uplo, alpha, x, A, true); }
+template <typename T>
+void Her(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& x, AbstractDistMatrix<T>& A) {
+    Syr(uplo, alpha, x, A, true);
+}
+// Syr2 / Her2 (Syr2.cpp): A += alpha (x y^T + y x^T) on the uplo triangle
+template <typename T>
+void Syr2(UpperOrLower uplo, T alpha, const AbstractMatrix<T>& x, const AbstractMatrix<T>& y, AbstractMatrix<T>& A,
+          bool /*conjugate*/ = false) {
+    if (x.GetDevice() != A.GetDevice() || y.GetDevice() != A.GetDevice())
+        throw LogicError("Syr2: x, y and A must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("A must be square: " + detail::Dims("A", A));
+    if (!detail::IsVec(x) || !detail::IsVec(y) || detail::VecLen(x) != A.Height() || detail::VecLen(y) != A.Height())
+        throw LogicError("Nonconformal Syr2: " + detail::Dims("A", A) + ", " + detail::Dims("x", x) + ", " +
+                         detail::Dims("y", y));
+    detail::LocalFence<T> fence(A, {&x, &y});
+    detail::Check(elx_matrix_syr2(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo, A.Height(),
+                                  detail::ToDouble(alpha), x.LockedBuffer(), detail::VecInc(x), y.LockedBuffer(),
+                                  detail::VecInc(y), A.Buffer(), A.LDim(), A.Stream()));
+}
+template <typename T, Device D>
+void Syr2(UpperOrLower uplo, T alpha, const Matrix<T, D>& x, const Matrix<T, D>& y, Matrix<T, D>& A,
+          bool conjugate = false) {
+    Syr2(uplo, alpha, static_cast<const AbstractMatrix<T>&>(x), static_cast<const AbstractMatrix<T>&>(y),
+         static_cast<AbstractMatrix<T>&>(A), conjugate);
+}
+template <typename T>
+void Syr2(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& x, const AbstractDistMatrix<T>& y,
+          AbstractDistMatrix<T>& A, bool conjugate = false) {
+    detail::Check(elx_syr2(uplo, detail::ToDouble(alpha), x.h(), y.h(), A.h(), conjugate));
+}
+template <typename T, Device D>
+void Her2(UpperOrLower uplo, T alpha, const Matrix<T, D>& x, const Matrix<T, D>& y, Matrix<T, D>& A) {
+    Syr2(uplo, alpha, x, y, A, true);
+}
+template <typename T>
+void Her2(UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& x, const AbstractDistMatrix<T>& y,
+          AbstractDistMatrix<T>& A) {
+    Syr2(uplo, alpha, x, y, A, true);
+}
 template <typename T>
 void Symm(LeftOrRight side, UpperOrLower uplo, T alpha, const AbstractDistMatrix<T>& A, const AbstractDistMatrix<T>& B,
           T beta, AbstractDistMatrix<T>& C, bool conjugate = false) {

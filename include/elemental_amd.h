@@ -239,6 +239,36 @@ int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
  * synchronize: on the GPU it is launches on the stream and nothing else.  f32/f64. */
 int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, void* tau, void* sig,
                   void* stream);
+/* ---- Level 2 on Matrix<T> (src/blas_like/level2): column-major A with any lda, vectors
+ * with an element stride >= 1 (a row of a Matrix has stride ldim).  Asynchronous on the
+ * stream; sums are kept in double (f64) or float (the other types) and rounded once; two
+ * calls on the same input give the same bits.
+ * El::Gemv: y := alpha op(A) x + beta y, A m x n.  beta == 0 overwrites y without reading
+ * it; alpha == 0 or a zero-length x gives y := beta y without reading A or x.  All four types */
+int elx_matrix_gemv(int dtype, int device, int orient, int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
+                    const void* x, int64_t incx, double beta, void* y, int64_t incy, void* stream);
+/* El::Ger / El::Geru: A += alpha x y^T, A m x n.  f32/f64 */
+int elx_matrix_ger(int dtype, int device, int64_t m, int64_t n, double alpha, const void* x, int64_t incx,
+                   const void* y, int64_t incy, void* A, int64_t lda, void* stream);
+/* El::Symv / El::Hemv: y := alpha A x + beta y with the symmetric n x n A given by its uplo
+ * triangle; the other triangle is never read.  f32/f64 */
+int elx_matrix_symv(int dtype, int device, int uplo, int64_t n, double alpha, const void* A, int64_t lda, const void* x,
+                    int64_t incx, double beta, void* y, int64_t incy, void* stream);
+/* symv::LocalColAccumulateL / U on one m x n block whose element (i, j) is the global
+ * (i0 + i istride, j0 + j jstride): with ELX_LOWER (mirrored for ELX_UPPER)
+ *   z_row[i] += alpha sum_{j: gj <= gi} a(i,j) x_col[j],  z_col[j] += alpha sum_{i: gi > gj} a(i,j) x_row[i];
+ * x_row, z_row are indexed by local row, x_col, z_col by local column.  f32/f64 */
+int elx_matrix_symv_accumulate(int dtype, int device, int uplo, int64_t m, int64_t n, double alpha, const void* A,
+                               int64_t lda, const void* x_row, int64_t incxr, const void* x_col, int64_t incxc,
+                               void* z_row, int64_t inczr, void* z_col, int64_t inczc, int64_t i0, int64_t istride,
+                               int64_t j0, int64_t jstride, void* stream);
+/* El::Syr / El::Her: A += alpha x x^T on the uplo triangle of the n x n A; the other
+ * triangle is neither read nor written.  f32/f64 */
+int elx_matrix_syr(int dtype, int device, int uplo, int64_t n, double alpha, const void* x, int64_t incx, void* A,
+                   int64_t lda, void* stream);
+/* El::Syr2 / El::Her2: A += alpha (x y^T + y x^T) likewise.  f32/f64 */
+int elx_matrix_syr2(int dtype, int device, int uplo, int64_t n, double alpha, const void* x, int64_t incx,
+                    const void* y, int64_t incy, void* A, int64_t lda, void* stream);
 
 /* ---- BLAS-1 entrywise kernels (dtype-generic; scalars passed as double) --
  * Strides are element strides: X(i,j) = X[i*xcs + j*xrs].
@@ -592,6 +622,41 @@ int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X);
 /* the QR leaf kernel's panel width and its rows per workgroup (kGeqrfLeafCols, kGeqrfLeafRows) */
 int64_t elx_qr_leaf_cols(void);
 int64_t elx_qr_leaf_rows(void);
+/* ---- Level 2 on DistMatrices (src/blas_like/level2).  A vector is an n x 1 or a 1 x n
+ * DistMatrix of any distribution; A of another distribution than [MC,MR] goes through a
+ * [MC,MR] copy.  Real types: `conjugate` is accepted and changes nothing (Hemv = Symv,
+ * Her = Syr, Her2 = Syr2, Geru = Ger).  Nonconformal operands, mixed types, devices or
+ * grids are ELX_ERR_LOGIC.
+ * El::Gemv (Gemv/Normal.hpp, Gemv/Transpose.hpp): y := alpha op(A) x + beta y.  All four types */
+int elx_gemv(int orient, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y);
+/* the beta-less overload: y is aligned with A, resized to a column vector and zeroed first */
+int elx_gemv_resize(int orient, double alpha, elx_dm_t A, elx_dm_t x, elx_dm_t y);
+/* El::LocalGemv on operands already spread and aligned with A [MC,MR]: ELX_NORMAL takes x
+ * [MR,*] or [*,MR] and y [MC,*] or [*,MC]; ELX_TRANSPOSE / ELX_ADJOINT the two exchanged */
+int elx_local_gemv(int orient, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y);
+/* El::Ger / El::Geru (Ger.cpp): A += alpha x y^T.  float and double */
+int elx_ger(double alpha, elx_dm_t x, elx_dm_t y, elx_dm_t A);
+/* El::Symv / El::Hemv (Symv.cpp): y := alpha A x + beta y, A symmetric with only its uplo
+ * triangle read.  float and double */
+int elx_symv(int uplo, double alpha, elx_dm_t A, elx_dm_t x, double beta, elx_dm_t y, int conjugate);
+/* El::symv::LocalColAccumulate (Symv/L.hpp, Symv/U.hpp) on the local block of A [MC,MR]:
+ * z[MC,*] += alpha tri(A) x[MR,*] and z[MR,*] += alpha tri'(A)^T x[MC,*], tri the uplo
+ * triangle with and tri' without the diagonal; all four vectors are columns aligned with A */
+int elx_symv_local_col_accumulate(int uplo, double alpha, elx_dm_t A, elx_dm_t x_MC_STAR, elx_dm_t x_MR_STAR,
+                                  elx_dm_t z_MC_STAR, elx_dm_t z_MR_STAR, int conjugate);
+/* El::Syr / El::Her (Syr.cpp): A += alpha x x^T on the uplo triangle.  float and double */
+int elx_syr(int uplo, double alpha, elx_dm_t x, elx_dm_t A, int conjugate);
+/* El::Syr2 / El::Her2 (Syr2.cpp): A += alpha (x y^T + y x^T) on the uplo triangle.  float and double */
+int elx_syr2(int uplo, double alpha, elx_dm_t x, elx_dm_t y, elx_dm_t A, int conjugate);
+/* the Level-2 kernels' launch shapes: rows of A per workgroup of the A x kernel (also the
+ * row chunk in which the A^T x kernel splits its sum), columns per x chunk of the A x kernel
+ * (also the chunk in which it splits its sum), and the Symv kernel's square tile */
+int64_t elx_level2_gemv_rows(void);
+int64_t elx_level2_gemv_cols(void);
+int64_t elx_level2_symv_tile(void);
+/* how many ranges the summed dimension of an m x n Gemv is cut into on the GPU (1: one
+ * launch; more: partial sums in workspace and a fixed-order second launch) */
+int64_t elx_level2_gemv_splits(int orient, int64_t m, int64_t n);
 /* El::Symm / El::Hemm (src/blas_like/level3/Symm.cpp:55-80): C := alpha A B + beta C
  * (ELX_LEFT) or alpha B A + beta C (ELX_RIGHT); A symmetric, only its uplo triangle read */
 int elx_symm(int side, int uplo, double alpha, elx_dm_t A, elx_dm_t B, double beta, elx_dm_t C,
