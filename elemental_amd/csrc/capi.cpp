@@ -264,7 +264,7 @@ int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int d
         CheckLd(ldb, m, "B");
         const Device d = ToDevice(device);
         const DType t = ToDType(dtype);
-        if (t != DType::F64 && t != DType::F32) throw LogicError("Trmm: only float and double are supported");
+        RequireReal(t, "Trmm");
         if (m == 0 || n == 0) return;
         hipStream_t s = DevStream(d, stream);
         const bool lower = uplo == ELX_LOWER, trans = orient != ELX_NORMAL, unit = diag == ELX_UNIT;
@@ -279,31 +279,12 @@ int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int d
     });
 }
 
-int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
-    return Guard([&] {
-        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Cholesky: bad UpperOrLower ", uplo);
-        ELX_REQUIRE(n >= 0, "negative Cholesky dimension");
-        const Device d = ToDevice(device);
-        const DType t = ToDType(dtype);
-        if (t != DType::F64 && t != DType::F32) throw LogicError("Cholesky: only float and double are supported");
-        CheckLd(lda, n, "A");
-        if (n == 0) return;
-        // the buffer as the local block of a 1x1-grid [MC,MR] matrix: a large
-        // Matrix gets the blocked driver, not one leaf
-        static const auto grid = std::make_shared<Grid>(Comm::Self(), 1, ELX_COLUMN_MAJOR);
-        DistMatrix M(grid, t, Dist::MC, Dist::MR, d);
-        M.Attach(n, n, 0, 0, A, lda, 0);
-        if (d == Device::GPU) M.SetStream(DevStream(d, stream));
-        Cholesky(uplo, M);
-    });
-}
-
 int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, int32_t* piv, void* stream) {
     return Guard([&] {
         ELX_REQUIRE(m >= 0 && n >= 0, "negative LU dimension");
         const Device d = ToDevice(device);
         const DType t = ToDType(dtype);
-        if (t != DType::F64 && t != DType::F32) throw LogicError("LU: only float and double are supported");
+        RequireReal(t, "LU");
         CheckLd(lda, m, "A");
         if (m == 0 || n == 0) return;
         ELX_REQUIRE(piv != nullptr, "LU: null pivot array");
@@ -329,7 +310,7 @@ int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
         ELX_REQUIRE(m >= 0 && n >= 0, "negative QR dimension");
         const Device d = ToDevice(device);
         const DType t = ToDType(dtype);
-        if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
+        RequireReal(t, "QR");
         CheckLd(lda, m, "A");
         if (m == 0 || n == 0) return;
         ELX_REQUIRE(A != nullptr, "QR: null matrix");
@@ -340,16 +321,18 @@ int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
 }
 
 namespace {
-// The checks and the attachment elx_matrix_cholesky makes, for the three inverse
-// entry points: `run` gets the buffer as a 1x1-grid [MC,MR] matrix on the stream.
-int MatrixInverseOp(const char* who, int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream,
-                    const std::function<void(DistMatrix&)>& run) {
+// The checks and the attachment shared by the entry points that take one square
+// matrix and its triangle: `run` gets the buffer as the local block of a 1x1-grid
+// [MC,MR] matrix on the stream, so a large Matrix gets the blocked driver, not
+// one leaf.
+int SquareMatrixOp(const char* who, int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream,
+                   const std::function<void(DistMatrix&)>& run) {
     return Guard([&] {
         ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, who, ": bad UpperOrLower ", uplo);
         ELX_REQUIRE(n >= 0, "negative ", who, " dimension");
         const Device d = ToDevice(device);
         const DType t = ToDType(dtype);
-        if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+        RequireReal(t, who);
         CheckLd(lda, n, "A");
         if (n == 0) return;
         static const auto grid = std::make_shared<Grid>(Comm::Self(), 1, ELX_COLUMN_MAJOR);
@@ -361,20 +344,23 @@ int MatrixInverseOp(const char* who, int dtype, int device, int uplo, int64_t n,
 }
 }  // namespace
 
+int elx_matrix_cholesky(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
+    return SquareMatrixOp("Cholesky", dtype, device, uplo, n, A, lda, stream,
+                          [&](DistMatrix& M) { Cholesky(uplo, M); });
+}
 int elx_matrix_triangular_inverse(int dtype, int device, int uplo, int diag, int64_t n, void* A, int64_t lda,
                                   void* stream) {
-    return MatrixInverseOp("TriangularInverse", dtype, device, uplo, n, A, lda, stream, [&](DistMatrix& M) {
+    return SquareMatrixOp("TriangularInverse", dtype, device, uplo, n, A, lda, stream, [&](DistMatrix& M) {
         ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "TriangularInverse: bad UnitOrNonUnit ", diag);
         TriangularInverse(uplo, diag, M);
     });
 }
 int elx_matrix_trtrmm(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
-    return MatrixInverseOp("Trtrmm", dtype, device, uplo, n, A, lda, stream,
-                           [&](DistMatrix& M) { Trtrmm(uplo, M); });
+    return SquareMatrixOp("Trtrmm", dtype, device, uplo, n, A, lda, stream, [&](DistMatrix& M) { Trtrmm(uplo, M); });
 }
 int elx_matrix_hpd_inverse(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* stream) {
-    return MatrixInverseOp("HPDInverse", dtype, device, uplo, n, A, lda, stream,
-                           [&](DistMatrix& M) { HPDInverse(uplo, M); });
+    return SquareMatrixOp("HPDInverse", dtype, device, uplo, n, A, lda, stream,
+                          [&](DistMatrix& M) { HPDInverse(uplo, M); });
 }
 
 // ---- BLAS-1 --------------------------------------------------------------
@@ -406,13 +392,9 @@ int elx_copy2d_convert(int src_dtype, int dst_dtype, int64_t m, int64_t n, const
 // (indexing/impl.hpp:33-36,244-245), stored column-major with ld = its height.
 }  // extern "C"
 namespace {
-Device PackDev(int device) {
-    ELX_REQUIRE(device == ELX_DEVICE_CPU || device == ELX_DEVICE_GPU, "pack: bad device ", device);
-    return device == ELX_DEVICE_GPU ? Device::GPU : Device::CPU;
-}
 void RunCopies(int device, int dtype, const std::vector<kern::Copy2D>& d, bool axpy, double alpha, void* stream) {
     if (d.empty()) return;
-    const Device dev = PackDev(device);
+    const Device dev = ToDevice(device);
     exec::Copy2DBatch(dev, ToDType(dtype), d.data(), (int)d.size(), axpy, alpha, dev == Device::GPU ? S(stream) : nullptr);
 }
 // StridedPack / StridedUnpack (util.hpp:667-718): portion k + l*colStride holds
@@ -599,27 +581,25 @@ int elx_rendezvous_bcast(void* data, size_t bytes, int rank, int size, const cha
 }
 int elx_watchdog_stage(const char* name, double seconds) { return Guard([&] { WatchdogStage(name, seconds); }); }
 int elx_watchdog_epitaph(const char* text, int exit_code) { return Guard([&] { WatchdogEpitaph(text, exit_code); }); }
+// El::mpi's typed collectives (src/core/imports/mpi/*.hpp): counts in elements, the
+// device and the stream follow the communicator's kind
+namespace {
+Device CommDev(elx_comm_t c) { return c->c->kind() == Comm::Kind::RCCL ? Device::GPU : Device::CPU; }
+hipStream_t CommStream(elx_comm_t c, void* stream) { return CommDev(c) == Device::GPU ? S(stream) : nullptr; }
+}  // namespace
 int elx_comm_allgather(elx_comm_t c, int dtype, const void* send, void* recv, int64_t count, void* stream) {
     return Guard([&] {
         ELX_REQUIRE(count >= 0, "allgather: negative count ", count);
-        const Device d = c->c->kind() == Comm::Kind::RCCL ? Device::GPU : Device::CPU;
-        c->c->AllGather(ToDType(dtype), send, recv, count, d, d == Device::GPU ? S(stream) : nullptr);
+        c->c->AllGather(ToDType(dtype), send, recv, count, CommDev(c), CommStream(c, stream));
     });
 }
 int elx_comm_reduce_scatter(elx_comm_t c, int dtype, const void* send, void* recv, int64_t count, void* stream) {
     return Guard([&] {
         ELX_REQUIRE(count >= 0, "reduce_scatter: negative count ", count);
-        const Device d = c->c->kind() == Comm::Kind::RCCL ? Device::GPU : Device::CPU;
-        c->c->ReduceScatter(ToDType(dtype), send, recv, count, d, d == Device::GPU ? S(stream) : nullptr);
+        c->c->ReduceScatter(ToDType(dtype), send, recv, count, CommDev(c), CommStream(c, stream));
     });
 }
 int elx_comm_barrier(elx_comm_t c) { return Guard([&] { c->c->Barrier(); }); }
-// the rest of El::mpi's typed collectives (src/core/imports/mpi/*.hpp); counts in
-// elements, device from the communicator's kind, as above
-namespace {
-Device CommDev(elx_comm_t c) { return c->c->kind() == Comm::Kind::RCCL ? Device::GPU : Device::CPU; }
-hipStream_t CommStream(elx_comm_t c, void* stream) { return CommDev(c) == Device::GPU ? S(stream) : nullptr; }
-}  // namespace
 int elx_comm_split(elx_comm_t c, int color, int key, elx_comm_t* out) {
     return Guard([&] { *out = new elx_comm_s{c->c->Split(color, key)}; });
 }
@@ -997,7 +977,7 @@ void CheckUplo(const char* who, int uplo) {
 }
 DType RealType(const char* who, int dtype) {
     const DType t = ToDType(dtype);
-    if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+    RequireReal(t, who);
     return t;
 }
 }  // namespace

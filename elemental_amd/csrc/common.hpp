@@ -120,6 +120,10 @@ inline const char* DTypeName(DType t) {
     }
     return "?";
 }
+// the guard of every routine that exists in f32 / f64 only; `who` names the routine
+inline void RequireReal(DType t, const char* who) {
+    if (t != DType::F64 && t != DType::F32) throw LogicError(Cat(who, ": only float and double are supported"));
+}
 
 // Host-side 16-bit float conversions (round-to-nearest-even), used by the CPU
 // device path and by scalar conversion at the boundary.

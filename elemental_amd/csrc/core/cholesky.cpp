@@ -31,8 +31,7 @@ void Cholesky(int uplo, DistMatrix& APre) {
     ELX_TRACE("El::Cholesky");
     ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Cholesky: bad UpperOrLower ", uplo);
     if (APre.Height() != APre.Width()) throw LogicError("A must be square");
-    if (APre.Type() != DType::F64 && APre.Type() != DType::F32)
-        throw LogicError("Cholesky: only float and double are supported");
+    RequireReal(APre.Type(), "Cholesky");
     RWProxy Ap(APre);
     DistMatrix& A = Ap.Get();
     const Int n = A.Height();

@@ -12,10 +12,9 @@ using namespace detail;
 
 namespace {
 
-void RequireRealFloat(const DistMatrix& A, const char* who) {
+void RequireSquareReal(const DistMatrix& A, const char* who) {
     if (A.Height() != A.Width()) throw LogicError("A must be square");
-    if (A.Type() != DType::F64 && A.Type() != DType::F32)
-        throw LogicError(Cat(who, ": only float and double are supported"));
+    RequireReal(A.Type(), who);
 }
 
 Int LeafRows() { return std::max<Int>(1, std::min<Int>(Blocksize(), kern::kTrtriMax)); }
@@ -217,7 +216,7 @@ void TriangularInverse(int uplo, int diag, DistMatrix& APre) {
     ELX_TRACE("El::TriangularInverse");
     ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "TriangularInverse: bad UpperOrLower ", uplo);
     ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "TriangularInverse: bad UnitOrNonUnit ", diag);
-    RequireRealFloat(APre, "TriangularInverse");
+    RequireSquareReal(APre, "TriangularInverse");
     RWProxy Ap(APre);
     TriangularInverseMCMR(uplo == ELX_LOWER, diag, Ap.Get());
     Ap.Finish();
@@ -228,7 +227,7 @@ void TriangularInverse(int uplo, int diag, DistMatrix& APre) {
 void Trtrmm(int uplo, DistMatrix& APre, bool /*conjugate*/) {
     ELX_TRACE("El::Trtrmm");
     ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trtrmm: bad UpperOrLower ", uplo);
-    RequireRealFloat(APre, "Trtrmm");
+    RequireSquareReal(APre, "Trtrmm");
     RWProxy Ap(APre);
     TrtrmmMCMR(uplo == ELX_LOWER, Ap.Get());
     Ap.Finish();
@@ -242,7 +241,7 @@ void Trtrmm(int uplo, DistMatrix& APre, bool /*conjugate*/) {
 void HPDInverse(int uplo, DistMatrix& APre) {
     ELX_TRACE("El::HPDInverse");
     ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "HPDInverse: bad UpperOrLower ", uplo);
-    RequireRealFloat(APre, "HPDInverse");
+    RequireSquareReal(APre, "HPDInverse");
     RWProxy Ap(APre);
     DistMatrix& A = Ap.Get();
     Cholesky(uplo, A);

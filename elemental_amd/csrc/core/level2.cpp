@@ -20,10 +20,6 @@ bool IsColumn(const DistMatrix& v) { return v.Width() == 1 || v.Height() != 1; }
 Int Inc(const DistMatrix& v) { return IsColumn(v) ? 1 : v.LDim(); }
 std::string Dims(const char* name, const DistMatrix& M) { return Cat(name, " ~ ", M.Height(), " x ", M.Width()); }
 
-void RequireReal(const char* who, const DistMatrix& A) {
-    if (A.Type() != DType::F64 && A.Type() != DType::F32)
-        throw LogicError(Cat(who, ": only float and double are supported"));
-}
 void RequireUplo(const char* who, int uplo) {
     ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, who, ": bad UpperOrLower ", uplo);
 }
@@ -138,7 +134,7 @@ void LocalGemv(int orient, double alpha, const DistMatrix& A, const DistMatrix& 
 void Ger(double alpha, const DistMatrix& x, const DistMatrix& y, DistMatrix& APre) {
     ELX_TRACE("El::Ger");
     RequireTogether("Ger", APre, {&x, &y});
-    RequireReal("Ger", APre);
+    RequireReal(APre.Type(), "Ger");
     if (!IsVector(x) || !IsVector(y) || VecLen(x) != APre.Height() || VecLen(y) != APre.Width())
         throw LogicError(Cat("Nonconformal Ger: ", Dims("A", APre), ", ", Dims("x", x), ", ", Dims("y", y)));
     if (APre.Height() == 0 || APre.Width() == 0 || alpha == 0.0) return;
@@ -156,7 +152,7 @@ void Symv(int uplo, double alpha, const DistMatrix& APre, const DistMatrix& x, d
     ELX_TRACE("El::Symv");
     RequireUplo("Symv", uplo);
     RequireTogether("Symv", APre, {&x, &y});
-    RequireReal("Symv", APre);
+    RequireReal(APre.Type(), "Symv");
     if (APre.Height() != APre.Width()) throw LogicError(Cat("A must be square: ", Dims("A", APre)));
     const Int n = APre.Height();
     if (!IsVector(x) || !IsVector(y) || VecLen(x) != n || VecLen(y) != n)
@@ -196,7 +192,7 @@ void symv::LocalColAccumulate(int uplo, double alpha, const DistMatrix& A, const
     ELX_TRACE("El::symv::LocalColAccumulate");
     RequireUplo("LocalColAccumulate", uplo);
     RequireTogether("LocalColAccumulate", A, {&x_MC_STAR, &x_MR_STAR, &z_MC_STAR, &z_MR_STAR});
-    RequireReal("LocalColAccumulate", A);
+    RequireReal(A.Type(), "LocalColAccumulate");
     ELX_REQUIRE(A.ColDist() == Dist::MC && A.RowDist() == Dist::MR, "LocalColAccumulate: A must be [MC,MR]");
     if (A.Height() != A.Width()) throw LogicError(Cat("A must be square: ", Dims("A", A)));
     auto fits = [&](const DistMatrix& v, Dist d, int align) {
@@ -217,7 +213,7 @@ void Syr(int uplo, double alpha, const DistMatrix& x, DistMatrix& APre) {
     ELX_TRACE("El::Syr");
     RequireUplo("Syr", uplo);
     RequireTogether("Syr", APre, {&x});
-    RequireReal("Syr", APre);
+    RequireReal(APre.Type(), "Syr");
     if (APre.Height() != APre.Width()) throw LogicError(Cat("A must be square: ", Dims("A", APre)));
     if (!IsVector(x) || VecLen(x) != APre.Height())
         throw LogicError(Cat("Nonconformal Syr: ", Dims("A", APre), ", ", Dims("x", x)));
@@ -237,7 +233,7 @@ void Syr2(int uplo, double alpha, const DistMatrix& x, const DistMatrix& y, Dist
     ELX_TRACE("El::Syr2");
     RequireUplo("Syr2", uplo);
     RequireTogether("Syr2", APre, {&x, &y});
-    RequireReal("Syr2", APre);
+    RequireReal(APre.Type(), "Syr2");
     if (APre.Height() != APre.Width()) throw LogicError(Cat("A must be square: ", Dims("A", APre)));
     if (!IsVector(x) || !IsVector(y) || VecLen(x) != APre.Height() || VecLen(y) != APre.Height())
         throw LogicError(Cat("Nonconformal Syr2: ", Dims("A", APre), ", ", Dims("x", x), ", ", Dims("y", y)));

@@ -174,8 +174,7 @@ void TriangularFrontDoor(const char* name, const char* not_square, const char* n
     ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, name, ": bad UnitOrNonUnit ", diag);
     ELX_REQUIRE(&A.G() == &B.G(), name, ": matrices on different grids");
     ELX_REQUIRE(A.Type() == B.Type(), name, ": mixed types");
-    if (A.Type() != DType::F64 && A.Type() != DType::F32)
-        throw LogicError(Cat(name, ": only float and double are supported"));
+    RequireReal(A.Type(), name);
     if (A.Height() != A.Width()) throw LogicError(not_square);  // Trsm.cpp:142-143, Trmm.cpp:31-32
     if ((side == ELX_LEFT ? B.Height() : B.Width()) != A.Height()) throw LogicError(nonconformal);
     if (checkIfSingular && diag != ELX_UNIT && DiagonalHasZero(A)) throw SingularMatrixError();

@@ -80,7 +80,7 @@ struct LocalLUCall {
 }  // namespace
 
 void LocalLU(Device dev, DType t, Int m, Int n, void* A, Int ld, int* piv, int* info, int col0, hipStream_t s) {
-    if (t != DType::F64 && t != DType::F32) throw LogicError("LU: only float and double are supported");
+    RequireReal(t, "LU");
     const Int k = std::min(m, n);
     if (k <= 0) return;
     ELX_REQUIRE(ld >= m && piv && info, "LocalLU: bad arguments");
@@ -96,8 +96,7 @@ void LocalLU(Device dev, DType t, Int m, Int n, void* A, Int ld, int* piv, int* 
 
 void LU(DistMatrix& APre, Permutation& P) {
     ELX_TRACE("El::LU");
-    if (APre.Type() != DType::F64 && APre.Type() != DType::F32)
-        throw LogicError("LU: only float and double are supported");
+    RequireReal(APre.Type(), "LU");
     RWProxy Ap(APre);
     DistMatrix& A = Ap.Get();
     const Int m = A.Height(), n = A.Width(), k = std::min(m, n);
@@ -160,8 +159,7 @@ void SolveAfter(int orient, const DistMatrix& A, const Permutation& P, DistMatri
     ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "SolveAfter: bad orientation");
     if (A.Height() != A.Width()) throw LogicError("A must be square");
     if (A.Height() != B.Height()) throw LogicError("A and B must be the same height");
-    if (A.Type() != DType::F64 && A.Type() != DType::F32)
-        throw LogicError("LU: only float and double are supported");
+    RequireReal(A.Type(), "LU");
     if (P.Height() != A.Height()) throw LogicError("A and P must be the same height");
     if (orient == ELX_NORMAL) {
         P.PermuteRows(B);

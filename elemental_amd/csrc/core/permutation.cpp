@@ -195,8 +195,7 @@ void Permutation::PermuteRowsRange(DistMatrix& B, Int k0, Int k1, bool inverse) 
     ELX_REQUIRE(B.ColDist() == Dist::MC && B.RowDist() == Dist::MR, "PermuteRows: not an [MC,MR] matrix");
     ELX_REQUIRE(0 <= k0 && k0 <= k1 && k1 <= nswaps_, "PermuteRows: swaps [", k0, ",", k1, ") of ", nswaps_);
     if (B.Height() != height_) throw LogicError("P and B must be the same height");
-    if (B.Type() != DType::F64 && B.Type() != DType::F32)
-        throw LogicError("PermuteRows: only float and double are supported");
+    RequireReal(B.Type(), "PermuteRows");
     if (B.Dev() != dev_) throw LogicError("PermuteRows: P and B live on different devices");
     if (k1 == k0 || B.Width() == 0) return;
     if (dev_ == Device::GPU) StreamFence(stream_, B.Stream());

@@ -21,10 +21,6 @@ using namespace detail;
 
 namespace {
 
-void RequireReal(DType t) {
-    if (t != DType::F64 && t != DType::F32) throw LogicError("QR: only float and double are supported");
-}
-
 // reflectors applied at once by LocalQR: S stays a kApplyBlock-row triangle
 constexpr Int kApplyBlock = 128;
 
@@ -123,7 +119,7 @@ DMPtr Replicated(const DistMatrix& like, Int h, Int w) {
 }  // namespace
 
 void LocalQR(Device dev, DType t, Int m, Int n, void* A, Int ld, void* tau, void* sig, hipStream_t s) {
-    RequireReal(t);
+    RequireReal(t, "QR");
     const Int k = std::min(m, n);
     if (k <= 0) return;
     ELX_REQUIRE(ld >= m && A && tau && sig, "LocalQR: bad arguments");
@@ -141,7 +137,7 @@ void LocalQR(Device dev, DType t, Int m, Int n, void* A, Int ld, void* tau, void
 
 void QR(DistMatrix& APre, DistMatrix& t, DistMatrix& d) {
     ELX_TRACE("El::QR");
-    RequireReal(APre.Type());
+    RequireReal(APre.Type(), "QR");
     ELX_REQUIRE(&APre.G() == &t.G() && &APre.G() == &d.G(), "QR: matrices on different grids");
     ELX_REQUIRE(APre.Type() == t.Type() && APre.Type() == d.Type(), "QR: mixed types");
     RWProxy Ap(APre);
@@ -187,7 +183,7 @@ void ApplyQ(int side, int orient, const DistMatrix& A, const DistMatrix& t, cons
     ELX_TRACE("El::qr::ApplyQ");
     if (side != ELX_LEFT) throw LogicError("ApplyQ: only LEFT is supported");
     ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "ApplyQ: bad orientation");
-    RequireReal(A.Type());
+    RequireReal(A.Type(), "QR");
     ELX_REQUIRE(&A.G() == &BPre.G() && &A.G() == &t.G() && &A.G() == &d.G(), "ApplyQ: matrices on different grids");
     ELX_REQUIRE(A.Type() == BPre.Type() && A.Type() == t.Type() && A.Type() == d.Type(), "ApplyQ: mixed types");
     const Int m = A.Height(), k = std::min(m, A.Width());
@@ -224,7 +220,7 @@ void SolveAfter(int orient, const DistMatrix& A, const DistMatrix& t, const Dist
                 DistMatrix& X) {
     ELX_TRACE("El::qr::SolveAfter");
     ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "SolveAfter: bad orientation");
-    RequireReal(A.Type());
+    RequireReal(A.Type(), "QR");
     const Int m = A.Height(), n = A.Width(), nrhs = B.Width();
     if (m < n) throw LogicError("Must have full column rank");
     if (B.Height() != (orient == ELX_NORMAL ? m : n)) throw LogicError("A and B do not conform");
@@ -252,7 +248,7 @@ void SolveAfter(int orient, const DistMatrix& A, const DistMatrix& t, const Dist
 
 void ExplicitTriang(DistMatrix& A) {
     ELX_TRACE("El::qr::ExplicitTriang");
-    RequireReal(A.Type());
+    RequireReal(A.Type(), "QR");
     const Int k = std::min(A.Height(), A.Width()), n = A.Width();
     auto t = A.Like(Dist::STAR, Dist::STAR), d = A.Like(Dist::STAR, Dist::STAR);
     QR(A, *t, *d);
@@ -265,7 +261,7 @@ void ExplicitTriang(DistMatrix& A) {
 
 void Explicit(DistMatrix& A, DistMatrix& R) {
     ELX_TRACE("El::qr::Explicit");
-    RequireReal(A.Type());
+    RequireReal(A.Type(), "QR");
     ELX_REQUIRE(&A.G() == &R.G(), "Explicit: matrices on different grids");
     ELX_REQUIRE(A.Type() == R.Type(), "Explicit: mixed types");
     const Int m = A.Height(), n = A.Width(), k = std::min(m, n);
@@ -291,7 +287,7 @@ void Explicit(DistMatrix& A, DistMatrix& R) {
 void LeastSquares(int orient, const DistMatrix& A, const DistMatrix& B, DistMatrix& X) {
     ELX_TRACE("El::LeastSquares");
     ELX_REQUIRE(orient >= ELX_NORMAL && orient <= ELX_ADJOINT, "LeastSquares: bad orientation");
-    RequireReal(A.Type());
+    RequireReal(A.Type(), "QR");
     if (A.Height() < A.Width()) throw UnsupportedError("LeastSquares: m < n (LQ) is not supported");
     if (B.Height() != (orient == ELX_NORMAL ? A.Height() : A.Width())) throw LogicError("A and B do not conform");
     auto F = A.Like(Dist::MC, Dist::MR);

@@ -17,8 +17,7 @@
 // (pitch 65: conflict-free both ways).
 #include <hip/hip_runtime.h>
 #include "kernels.hpp"
-#include "elem.hpp"
-#include "../../../include/elemental_amd.h"
+#include "dtype_switch.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
@@ -616,15 +615,6 @@ dim3 grid2d(i64 m, i64 n) {
     return dim3((unsigned)gx, (unsigned)gy);
 }
 
-#define ELX_DTYPE_SWITCH(dtype, T, ...)                 \
-    switch (dtype) {                                    \
-    case ELX_F64: { using T = double; __VA_ARGS__; break; } \
-    case ELX_F32: { using T = float; __VA_ARGS__; break; }  \
-    case ELX_F16: { using T = f16_t; __VA_ARGS__; break; }  \
-    case ELX_BF16: { using T = bf16_t; __VA_ARGS__; break; } \
-    default: return hipErrorInvalidValue;               \
-    }
-
 // A transposing descriptor whose unit-stride runs are 16-B aligned on both
 // sides (the condition of copy2d_kernel's `tvec` branch): transpose_vec_kernel.
 bool TransposeVec(const Copy2D& x, int es) {
@@ -685,7 +675,8 @@ hipError_t copy2d_batch(int dtype, const Copy2D* d, int nd, bool axpy, double al
         i64 maxtiles = 0, maxvec = 0, maxwt = 0;
         int used = 0;
         bool cols = true, tvec_all = true;
-        const int es = dtype == ELX_F64 ? 8 : dtype == ELX_F32 ? 4 : 2;
+        const int es = dtype_size(dtype);
+        if (es == 0) return hipErrorInvalidValue;
         for (int q = 0; q < cnt; ++q) {
             Copy2D x = d[base + q];
             if (x.m <= 0 || x.n <= 0) continue;
@@ -715,20 +706,20 @@ hipError_t copy2d_batch(int dtype, const Copy2D* d, int nd, bool axpy, double al
             // ~8 workgroups per CU: 32 waves per CU over the batch's wave tiles
             const unsigned gx = (unsigned)std::max<i64>(1, std::min<i64>(std::min<i64>((maxwt + 3) / 4, 2048), cap));
             dim3 grid(gx, used);
-            ELX_DTYPE_SWITCH(dtype, T,
+            ELX_KERN_SWITCH(dtype, T,
                 if (axpy) hipLaunchKernelGGL((transpose_vec_kernel<T, true>), grid, dim3(NT), 0, s, b, alpha);
                 else hipLaunchKernelGGL((transpose_vec_kernel<T, false>), grid, dim3(NT), 0, s, b, alpha));
         } else if (cols) {
             // ~16 workgroups per CU across the batch
             const i64 gx = std::max<i64>(1, std::min<i64>(std::min<i64>((maxvec + NT * UNROLL - 1) / (NT * UNROLL), 1 << 20), cap));
             dim3 grid((unsigned)gx, used);
-            ELX_DTYPE_SWITCH(dtype, T,
+            ELX_KERN_SWITCH(dtype, T,
                 if (axpy) hipLaunchKernelGGL((copy_cols_kernel<T, true>), grid, dim3(NT), 0, s, b, alpha);
                 else hipLaunchKernelGGL((copy_cols_kernel<T, false>), grid, dim3(NT), 0, s, b, alpha));
         } else {
             const unsigned gx = (unsigned)std::max<i64>(1, std::min<i64>(maxtiles > 4096 ? 4096 : maxtiles, cap));
             dim3 grid(gx, used);
-            ELX_DTYPE_SWITCH(dtype, T,
+            ELX_KERN_SWITCH(dtype, T,
                 if (axpy) hipLaunchKernelGGL((copy2d_kernel<T, true>), grid, dim3(NT), 0, s, b, alpha);
                 else hipLaunchKernelGGL((copy2d_kernel<T, false>), grid, dim3(NT), 0, s, b, alpha));
         }
@@ -741,14 +732,15 @@ hipError_t copy2d_batch(int dtype, const Copy2D* d, int nd, bool axpy, double al
 hipError_t contract_sum(int dtype, const ContractSum& c, double alpha, hipStream_t s, int max_wgs) {
     if (c.m <= 0 || c.n <= 0 || c.nsrc <= 0) return hipSuccess;
     if (c.nsrc > kMaxContractSources) return hipErrorInvalidValue;
-    const int es = dtype == ELX_F64 ? 8 : dtype == ELX_F32 ? 4 : 2;
+    const int es = dtype_size(dtype);
+    if (es == 0) return hipErrorInvalidValue;
     const i64 mv = (c.m + 16 / es - 1) / (16 / es);
     // ~8 workgroups per CU in total, under the caller's cap
     const i64 gy = std::min<i64>(c.n, 4096);
     i64 gx = std::max<i64>(1, std::min<i64>((mv + NT - 1) / NT, std::max<i64>(1, 2048 / gy)));
     if (max_wgs > 0) gx = std::max<i64>(1, std::min<i64>(gx, max_wgs / gy));
     const dim3 grid((unsigned)gx, (unsigned)gy);
-    ELX_DTYPE_SWITCH(dtype, T, hipLaunchKernelGGL((contract_sum_kernel<T>), grid, dim3(NT), 0, s, c, alpha));
+    ELX_KERN_SWITCH(dtype, T, hipLaunchKernelGGL((contract_sum_kernel<T>), grid, dim3(NT), 0, s, c, alpha));
     return hipGetLastError();
 }
 
@@ -757,13 +749,13 @@ hipError_t convert2d(int sdt, int ddt, const Copy2D& d, hipStream_t s) {
     if (sdt == ddt) return copy2d_batch(sdt, &d, 1, false, 0.0, s);
     const i64 tiles = ((d.m + TILE - 1) / TILE) * ((d.n + TILE - 1) / TILE);
     const dim3 grid((unsigned)(tiles > 8192 ? 8192 : tiles));
-    ELX_DTYPE_SWITCH(sdt, TS, ELX_DTYPE_SWITCH(ddt, TD, hipLaunchKernelGGL((convert2d_kernel<TS, TD>), grid, dim3(NT), 0, s, d)));
+    ELX_KERN_SWITCH(sdt, TS, ELX_KERN_SWITCH(ddt, TD, hipLaunchKernelGGL((convert2d_kernel<TS, TD>), grid, dim3(NT), 0, s, d)));
     return hipGetLastError();
 }
 
 hipError_t fill2d(int dtype, i64 m, i64 n, double v, void* A, i64 lda, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    ELX_DTYPE_SWITCH(dtype, T, {
+    ELX_KERN_SWITCH(dtype, T, {
         const EwShape g = ew_shape<typename Elem<T>::storage>(m, n, {{A, lda}});
         hipLaunchKernelGGL((fill_kernel<T>), g.grid, dim3(NT), 0, s, g.m, g.n, v,
                            static_cast<typename Elem<T>::storage*>(A), lda, g.vec);
@@ -777,7 +769,7 @@ hipError_t norm_partials(int dtype, int mode, i64 m, i64 n, const void* A, i64 l
     if (m <= 0 || n <= 0) return hipSuccess;
     const dim3 grid((unsigned)std::min<i64>((m + NT - 1) / NT, 32), (unsigned)std::min<i64>(n, kNormPartsMax / 32));
     *nparts = (int)(grid.x * grid.y);
-    ELX_DTYPE_SWITCH(dtype, T, {
+    ELX_KERN_SWITCH(dtype, T, {
         using S = typename Elem<T>::storage;
         if (mode == 0)
             hipLaunchKernelGGL((norm_partial_kernel<T, 0>), grid, dim3(NT), 0, s, m, n, static_cast<const S*>(A), lda,
@@ -791,7 +783,7 @@ hipError_t norm_partials(int dtype, int mode, i64 m, i64 n, const void* A, i64 l
 
 hipError_t scale2d(int dtype, i64 m, i64 n, double alpha, void* A, i64 lda, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    ELX_DTYPE_SWITCH(dtype, T, {
+    ELX_KERN_SWITCH(dtype, T, {
         const EwShape g = ew_shape<typename Elem<T>::storage>(m, n, {{A, lda}});
         hipLaunchKernelGGL((scale_kernel<T>), g.grid, dim3(NT), 0, s, g.m, g.n, alpha,
                            static_cast<typename Elem<T>::storage*>(A), lda, g.vec);
@@ -802,7 +794,7 @@ hipError_t scale2d(int dtype, i64 m, i64 n, double alpha, void* A, i64 lda, hipS
 hipError_t hadamard2d(int dtype, i64 m, i64 n, const void* A, i64 lda, const void* B, i64 ldb, void* C,
                       i64 ldc, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    ELX_DTYPE_SWITCH(dtype, T, {
+    ELX_KERN_SWITCH(dtype, T, {
         using S = typename Elem<T>::storage;
         const EwShape g = ew_shape<S>(m, n, {{A, lda}, {B, ldb}, {C, ldc}});
         hipLaunchKernelGGL((hadamard_kernel<T>), g.grid, dim3(NT), 0, s, g.m, g.n,
@@ -824,7 +816,7 @@ hipError_t entrywise_map(int dtype, int fn, i64 m, i64 n, const void* A, i64 lda
                          hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
 #define ELX_MAP_CASE(F) case F: launch_map<T, F>(s, m, n, A, lda, B, ldb); break;
-    ELX_DTYPE_SWITCH(dtype, T, switch (fn) {
+    ELX_KERN_SWITCH(dtype, T, switch (fn) {
         ELX_MAP_CASE(ELX_MAP_IDENTITY) ELX_MAP_CASE(ELX_MAP_NEGATE) ELX_MAP_CASE(ELX_MAP_ABS)
         ELX_MAP_CASE(ELX_MAP_SQUARE) ELX_MAP_CASE(ELX_MAP_SQRT) ELX_MAP_CASE(ELX_MAP_EXP)
         ELX_MAP_CASE(ELX_MAP_LOG) ELX_MAP_CASE(ELX_MAP_RELU) ELX_MAP_CASE(ELX_MAP_SIGMOID)
@@ -846,7 +838,7 @@ static void launch_combine(hipStream_t s, i64 m, i64 n, const void* A, i64 lda, 
 hipError_t combine(int dtype, int fn, i64 m, i64 n, const void* A, i64 lda, void* B, i64 ldb, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
 #define ELX_COMBINE_CASE(F) case F: launch_combine<T, F>(s, m, n, A, lda, B, ldb); break;
-    ELX_DTYPE_SWITCH(dtype, T, switch (fn) {
+    ELX_KERN_SWITCH(dtype, T, switch (fn) {
         ELX_COMBINE_CASE(ELX_COMBINE_ADD) ELX_COMBINE_CASE(ELX_COMBINE_SUB) ELX_COMBINE_CASE(ELX_COMBINE_MUL)
         ELX_COMBINE_CASE(ELX_COMBINE_DIV) ELX_COMBINE_CASE(ELX_COMBINE_MAX) ELX_COMBINE_CASE(ELX_COMBINE_MIN)
         ELX_COMBINE_CASE(ELX_COMBINE_RELU_GRAD)
@@ -859,7 +851,7 @@ hipError_t combine(int dtype, int fn, i64 m, i64 n, const void* A, i64 lda, void
 hipError_t fill_hash(int dtype, i64 m, i64 n, void* A, i64 lda, i64 i0, i64 istride, i64 j0, i64 jstride,
                      uint64_t seed, double center, double radius, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    ELX_DTYPE_SWITCH(dtype, T,
+    ELX_KERN_SWITCH(dtype, T,
         hipLaunchKernelGGL((hash_kernel<T>), grid2d(m, n), dim3(NT), 0, s, m, n,
                            static_cast<typename Elem<T>::storage*>(A), lda, i0, istride, j0, jstride,
                            seed, center, radius));
@@ -869,7 +861,7 @@ hipError_t fill_hash(int dtype, i64 m, i64 n, void* A, i64 lda, i64 i0, i64 istr
 hipError_t trapezoid2d(int dtype, bool lower, i64 m, i64 n, double alpha, const void* X, i64 ldx, double beta,
                        void* Y, i64 ldy, i64 i0, i64 istride, i64 j0, i64 jstride, i64 offset, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    ELX_DTYPE_SWITCH(dtype, T,
+    ELX_KERN_SWITCH(dtype, T,
         hipLaunchKernelGGL((trapezoid_kernel<T>), grid2d(m, n), dim3(NT), 0, s, lower, m, n, alpha,
                            static_cast<const typename Elem<T>::storage*>(X), ldx, beta,
                            static_cast<typename Elem<T>::storage*>(Y), ldy, i0, istride, j0, jstride, offset));

@@ -42,6 +42,7 @@
 //   qr_fix_t        T := tril(T) with diag(T) = 1 / t (FixDiagonal)
 //   row_scale       A(i, :) *= sig[i0 + i * istride]
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "../common.hpp"
 #include <climits>
 
@@ -281,29 +282,18 @@ size_t geqrf_work_bytes(i64 m) {
 hipError_t geqrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, void* tau, void* sig, void* work, hipStream_t s) {
     if (m <= 0 || w <= 0) return hipSuccess;
     if (w > W || m > INT_MAX - R || lda < m || !A || !tau || !sig || !work) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_leaf(m, w, static_cast<double*>(A), lda, static_cast<double*>(tau), static_cast<double*>(sig),
-                           work, s);
-    case ELX_F32:
-        return launch_leaf(m, w, static_cast<float*>(A), lda, static_cast<float*>(tau), static_cast<float*>(sig), work,
-                           s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_leaf(m, w, static_cast<T*>(A), lda, static_cast<T*>(tau), static_cast<T*>(sig), work,
+                                       s));
 }
 
 hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s) {
     if (m <= 0 || nb <= 0) return hipSuccess;
     if (lda < m || ldu < m || nb > 65535 || m > (i64)256 * INT_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((m + 255) / 256), (unsigned)nb);
-    if (dtype == ELX_F64)
-        hipLaunchKernelGGL((qr_explicit_u_kernel<double>), grid, dim3(256), 0, s, m, nb, static_cast<const double*>(A),
-                           lda, static_cast<double*>(U), ldu);
-    else if (dtype == ELX_F32)
-        hipLaunchKernelGGL((qr_explicit_u_kernel<float>), grid, dim3(256), 0, s, m, nb, static_cast<const float*>(A),
-                           lda, static_cast<float*>(U), ldu);
-    else return hipErrorInvalidValue;
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    hipLaunchKernelGGL((qr_explicit_u_kernel<T>), grid, dim3(256), 0, s, m, nb,
+                                       static_cast<const T*>(A), lda, static_cast<T*>(U), ldu));
     return hipGetLastError();
 }
 
@@ -311,13 +301,9 @@ hipError_t qr_fix_t(int dtype, i64 nb, void* S, i64 lds, const void* tau, hipStr
     if (nb <= 0) return hipSuccess;
     if (lds < nb || nb > 65535 || !tau) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((nb + 255) / 256), (unsigned)nb);
-    if (dtype == ELX_F64)
-        hipLaunchKernelGGL((qr_fix_t_kernel<double>), grid, dim3(256), 0, s, nb, static_cast<double*>(S), lds,
-                           static_cast<const double*>(tau));
-    else if (dtype == ELX_F32)
-        hipLaunchKernelGGL((qr_fix_t_kernel<float>), grid, dim3(256), 0, s, nb, static_cast<float*>(S), lds,
-                           static_cast<const float*>(tau));
-    else return hipErrorInvalidValue;
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    hipLaunchKernelGGL((qr_fix_t_kernel<T>), grid, dim3(256), 0, s, nb, static_cast<T*>(S), lds,
+                                       static_cast<const T*>(tau)));
     return hipGetLastError();
 }
 
@@ -325,13 +311,9 @@ hipError_t row_scale(int dtype, i64 m, i64 n, void* A, i64 lda, const void* sig,
     if (m <= 0 || n <= 0) return hipSuccess;
     if (lda < m || !sig || m > (i64)256 * INT_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((m + 255) / 256), (unsigned)std::min<i64>(n, 1024));
-    if (dtype == ELX_F64)
-        hipLaunchKernelGGL((row_scale_kernel<double>), grid, dim3(256), 0, s, m, n, static_cast<double*>(A), lda,
-                           static_cast<const double*>(sig), i0, is);
-    else if (dtype == ELX_F32)
-        hipLaunchKernelGGL((row_scale_kernel<float>), grid, dim3(256), 0, s, m, n, static_cast<float*>(A), lda,
-                           static_cast<const float*>(sig), i0, is);
-    else return hipErrorInvalidValue;
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    hipLaunchKernelGGL((row_scale_kernel<T>), grid, dim3(256), 0, s, m, n, static_cast<T*>(A), lda,
+                                       static_cast<const T*>(sig), i0, is));
     return hipGetLastError();
 }
 

@@ -35,6 +35,7 @@
 // stores col0 + j + 1 into *info if that is still 0, and every launch that finds
 // *info != 0 does nothing (the info-word contract of potrf_kernel).
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "../common.hpp"
 #include <climits>
 
@@ -350,28 +351,16 @@ hipError_t getrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, int* piv, int r
                       int col0, hipStream_t s) {
     if (m <= 0 || w <= 0) return hipSuccess;
     if (w > W || w > m || m > INT_MAX - R || lda < m || !piv || !work || !info) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_leaf(m, w, static_cast<double*>(A), lda, piv, row_off, work, info, col0, s);
-    case ELX_F32:
-        return launch_leaf(m, w, static_cast<float*>(A), lda, piv, row_off, work, info, col0, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_leaf(m, w, static_cast<T*>(A), lda, piv, row_off, work, info, col0, s));
 }
 
 hipError_t laswp(int dtype, i64 m, i64 ncols, void* A, i64 lda, const int* piv, i64 k0, i64 k1, i64 voff, bool inverse,
                  const int* info, hipStream_t s) {
     if (m <= 0 || ncols <= 0 || k1 <= k0) return hipSuccess;
     if (lda < m || !piv || k0 < 0 || ncols > (i64)256 * INT_MAX) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_laswp(m, ncols, static_cast<double*>(A), lda, piv, k0, k1, voff, inverse, info, s);
-    case ELX_F32:
-        return launch_laswp(m, ncols, static_cast<float*>(A), lda, piv, k0, k1, voff, inverse, info, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_laswp(m, ncols, static_cast<T*>(A), lda, piv, k0, k1, voff, inverse, info, s));
 }
 
 }  // namespace kern

@@ -16,8 +16,7 @@
 // NT / RL column groups take the tile's columns round-robin.
 #include <hip/hip_runtime.h>
 #include "kernels.hpp"
-#include "elem.hpp"
-#include "../../../include/elemental_amd.h"
+#include "dtype_switch.hpp"
 #include <algorithm>
 
 namespace elx {
@@ -410,22 +409,6 @@ bool Aligned16(const void* p, i64 ld, size_t es) {
     return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (ld * (i64)es) % 16 == 0;
 }
 
-#define ELX_L2_SWITCH(dtype, T, ...)                            \
-    switch (dtype) {                                            \
-    case ELX_F64: { using T = double; __VA_ARGS__; break; }     \
-    case ELX_F32: { using T = float; __VA_ARGS__; break; }      \
-    case ELX_F16: { using T = f16_t; __VA_ARGS__; break; }      \
-    case ELX_BF16: { using T = bf16_t; __VA_ARGS__; break; }    \
-    default: return hipErrorInvalidValue;                       \
-    }
-// the four routines that exist in f64 / f32 only
-#define ELX_L2_REAL_SWITCH(dtype, T, ...)                       \
-    switch (dtype) {                                            \
-    case ELX_F64: { using T = double; __VA_ARGS__; break; }     \
-    case ELX_F32: { using T = float; __VA_ARGS__; break; }      \
-    default: return hipErrorInvalidValue;                       \
-    }
-
 template <typename T>
 hipError_t gemv_t(bool trans, i64 m, i64 n, double alpha, const void* A_, i64 lda, const void* x_, i64 incx,
                   double beta, void* y_, i64 incy, hipStream_t s) {
@@ -501,13 +484,13 @@ hipError_t gemv(int dtype, bool trans, i64 m, i64 n, double alpha, const void* A
     if (xlen <= 0 || alpha == 0.0) return vec_scale(dtype, ylen, beta, y, incy, s);
     if ((m + kGemvRows - 1) / kGemvRows > 0x7fffffffll || (n + kGemvTCols - 1) / kGemvTCols > 0x7fffffffll)
         return hipErrorInvalidValue;
-    ELX_L2_SWITCH(dtype, T, return gemv_t<T>(trans, m, n, alpha, A, lda, x, incx, beta, y, incy, s));
+    ELX_KERN_SWITCH(dtype, T, return gemv_t<T>(trans, m, n, alpha, A, lda, x, incx, beta, y, incy, s));
     return hipSuccess;
 }
 
 hipError_t vec_scale(int dtype, i64 len, double beta, void* y, i64 incy, hipStream_t s) {
     if (len <= 0 || beta == 1.0) return hipSuccess;
-    ELX_L2_SWITCH(dtype, T, launch_reduce<T>(len, 0.0, nullptr, 0, nullptr, 0, beta, y, incy, false, TriMap{}, s));
+    ELX_KERN_SWITCH(dtype, T, launch_reduce<T>(len, 0.0, nullptr, 0, nullptr, 0, beta, y, incy, false, TriMap{}, s));
     return hipGetLastError();
 }
 
@@ -523,7 +506,7 @@ hipError_t symv(int dtype, bool lower, i64 m, i64 n, double alpha, const void* A
     const i64 nti = (m + kSymvTile - 1) / kSymvTile, ntj = (n + kSymvTile - 1) / kSymvTile;
     if (ntj > 65535 || nti > 0x7fffffffll) return hipErrorInvalidValue;
     const TriMap mp{lower ? 1 : 0, m, n, i0, is, j0, js};
-    ELX_L2_REAL_SWITCH(dtype, T, {
+    ELX_KERN_REAL_SWITCH(dtype, T, {
         using S = typename Elem<T>::storage;
         using C = typename Elem<T>::compute;
         C* part = nullptr;
@@ -557,7 +540,7 @@ hipError_t rank_update(int dtype, int terms, bool lower, i64 m, i64 n, double al
     if (terms < 0 || terms > 2 || is < 1 || js < 1) return hipErrorInvalidValue;
     const i64 gx = (m + kGerRows - 1) / kGerRows;
     if (gx > 0x7fffffffll) return hipErrorInvalidValue;
-    ELX_L2_REAL_SWITCH(dtype, T, {
+    ELX_KERN_REAL_SWITCH(dtype, T, {
         using S = typename Elem<T>::storage;
         using C = typename Elem<T>::compute;
         const bool vec = Aligned16(A, lda, sizeof(S));

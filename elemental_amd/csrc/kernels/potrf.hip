@@ -22,6 +22,7 @@
 // goes to *info (one ordinary store from one lane) and nothing is written back.
 // A launch that finds *info != 0 returns at once.
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "mfma_tile.hpp"
 #include "../common.hpp"
 
@@ -172,14 +173,8 @@ static_assert(potrf_lds<double>(kPotrfMax) <= 160 * 1024, "kPotrfMax: the f64 bl
 hipError_t potrf_block(int dtype, bool lower, i64 n, void* A, i64 lda, int* info, int col0, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > kPotrfMax || lda < n || !info) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_potrf(lower, n, static_cast<double*>(A), lda, info, col0, s);
-    case ELX_F32:
-        return launch_potrf(lower, n, static_cast<float*>(A), lda, info, col0, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_potrf(lower, n, static_cast<T*>(A), lda, info, col0, s));
 }
 
 }  // namespace kern

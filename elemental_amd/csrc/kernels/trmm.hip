@@ -19,14 +19,16 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "../common.hpp"
 #include "mfma_tile.hpp"
 
 namespace elx {
 namespace kern {
 
-using TrmmTile64 = TileCfg<kTrmmBM64, 64, 4, 2, 2>;   // f64: 8 waves of 32x32, 4 per SIMD
-using TrmmTile32 = TileCfg<kTrmmBM32, 128, 4, 2, 1>;  // f32: 8 waves of 64x64, 2 per SIMD
+template <typename T> struct TrmmTile;
+template <> struct TrmmTile<double> { using type = TileCfg<kTrmmBM64, 64, 4, 2, 2>; };  // 8 waves of 32x32, 4 per SIMD
+template <> struct TrmmTile<float> { using type = TileCfg<kTrmmBM32, 128, 4, 2, 1>; };  // 8 waves of 64x64, 2 per SIMD
 static_assert(kTrmmBK == BK, "trmm_krange's slab is the tile kernels' BK");
 
 template <typename T>
@@ -212,9 +214,10 @@ static hipError_t launch_trmm(TrmmParams<T> p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <typename T, typename CFG>
+template <typename T>
 static hipError_t trmm_typed(bool lower, bool trans, bool unit, i64 m, i64 n, double alpha, const void* A, i64 lda,
                              const void* B, i64 ldb, void* C, i64 ldc, hipStream_t s) {
+    using CFG = typename TrmmTile<T>::type;
     const TrmmParams<T> p{m, n, (T)alpha, static_cast<const T*>(A), lda, static_cast<const T*>(B), ldb,
                           static_cast<T*>(C), ldc, 0, 0, unit};
     if (trans) return lower ? launch_trmm<T, CFG, true, false>(p, s) : launch_trmm<T, CFG, true, true>(p, s);
@@ -225,11 +228,8 @@ hipError_t trmm_tri(int dtype, bool lower, bool trans, bool unit, i64 m, i64 n, 
                     const void* B, i64 ldb, void* C, i64 ldc, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
     if (lda < m || ldb < m || ldc < m) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64: return trmm_typed<double, TrmmTile64>(lower, trans, unit, m, n, alpha, A, lda, B, ldb, C, ldc, s);
-    case ELX_F32: return trmm_typed<float, TrmmTile32>(lower, trans, unit, m, n, alpha, A, lda, B, ldb, C, ldc, s);
-    default: return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return trmm_typed<T>(lower, trans, unit, m, n, alpha, A, lda, B, ldb, C, ldc, s));
 }
 
 }  // namespace kern

@@ -13,6 +13,7 @@
 // so with many right-hand sides exec::Trsm instead inverts the block (IDENT: the
 // identity as right-hand sides, m lanes) and applies op(A)^-1 as one MFMA GEMM.
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "../common.hpp"
 
 namespace elx {
@@ -112,63 +113,60 @@ hipError_t launch_trsm(bool ident, bool lower, bool trans, bool unit, i64 m, i64
     return hipGetLastError();
 }
 
+// LDS of one block's substitution: nb rows of 64 lanes, padded
+template <typename T>
+size_t tri_inverse_lds(i64 nb) { return (size_t)nb * (WAVE + 1) * sizeof(T); }
+
+// beyond the default dynamic-LDS limit (gfx950: 160 KiB per workgroup)
+template <typename T>
+hipError_t raise_tri_inverse_lds(size_t lds) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&tri_inverse_batched_kernel<T>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+template <typename T>
+bool tri_inverse_lds_ok_t(i64 nb) {
+    const size_t lds = tri_inverse_lds<T>(nb);
+    if (lds > (size_t)kTriInverseLdsMax) return false;
+    return lds <= 64 * 1024 || raise_tri_inverse_lds<T>(lds) == hipSuccess;
+}
+
+template <typename T>
+hipError_t launch_tri_inverse_batched(bool lower, bool trans, bool unit, i64 nb, i64 m, const T* A, i64 lda, T* W,
+                                      hipStream_t s) {
+    const i64 nblk = (m + nb - 1) / nb;
+    const size_t lds = tri_inverse_lds<T>(nb);
+    if (lds > (size_t)kTriInverseLdsMax || nblk > 65535) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((nb + WAVE - 1) / WAVE), (unsigned)nblk);
+    if (lds > 64 * 1024) {
+        const hipError_t e = raise_tri_inverse_lds<T>(lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((tri_inverse_batched_kernel<T>), grid, dim3(WAVE), lds, s, lower, trans, unit, nb, m, A, lda, W);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 bool tri_inverse_lds_ok(int dtype, i64 nb) {
-    const int es = dtype == ELX_F64 ? 8 : 4;
-    const size_t lds = (size_t)nb * (WAVE + 1) * es;
-    if (lds > (size_t)kTriInverseLdsMax || (dtype != ELX_F64 && dtype != ELX_F32)) return false;
-    if (lds <= 64 * 1024) return true;
-    const void* f = dtype == ELX_F64 ? reinterpret_cast<const void*>(&tri_inverse_batched_kernel<double>)
-                                     : reinterpret_cast<const void*>(&tri_inverse_batched_kernel<float>);
-    return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    ELX_REAL_SWITCH(dtype, T, return false, return tri_inverse_lds_ok_t<T>(nb));
 }
 
 hipError_t tri_inverse_batched(int dtype, bool lower, bool trans, bool unit, i64 nb, i64 m, const void* A, i64 lda,
                                void* W, hipStream_t s) {
     if (m <= 0 || nb <= 0) return hipSuccess;
-    const i64 nblk = (m + nb - 1) / nb;
-    const int es = dtype == ELX_F64 ? 8 : 4;
-    const size_t lds = (size_t)nb * (WAVE + 1) * es;
-    if (lds > (size_t)kTriInverseLdsMax || nblk > 65535) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((nb + WAVE - 1) / WAVE), (unsigned)nblk);
-    switch (dtype) {
-    case ELX_F64:
-        if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit (gfx950: 160 KiB per workgroup)
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tri_inverse_batched_kernel<double>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((tri_inverse_batched_kernel<double>), grid, dim3(WAVE), lds, s, lower, trans, unit, nb, m,
-                           static_cast<const double*>(A), lda, static_cast<double*>(W));
-        break;
-    case ELX_F32:
-        if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tri_inverse_batched_kernel<float>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((tri_inverse_batched_kernel<float>), grid, dim3(WAVE), lds, s, lower, trans, unit, nb, m,
-                           static_cast<const float*>(A), lda, static_cast<float*>(W));
-        break;
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_tri_inverse_batched(lower, trans, unit, nb, m, static_cast<const T*>(A), lda,
+                                                      static_cast<T*>(W), s));
 }
 
 hipError_t trsm_local(int dtype, bool ident, bool lower, bool trans, bool unit, i64 m, i64 n, const void* A, i64 lda,
                       void* B, i64 ldb, hipStream_t s) {
     if (m <= 0 || n <= 0) return hipSuccess;
     if (n > (i64)WAVE * 0x7fffffff) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_trsm(ident, lower, trans, unit, m, n, static_cast<const double*>(A), lda, static_cast<double*>(B), ldb, s);
-    case ELX_F32:
-        return launch_trsm(ident, lower, trans, unit, m, n, static_cast<const float*>(A), lda, static_cast<float*>(B), ldb, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_trsm(ident, lower, trans, unit, m, n, static_cast<const T*>(A), lda,
+                                       static_cast<T*>(B), ldb, s));
 }
 
 }  // namespace kern

@@ -31,6 +31,7 @@
 //   36 tiles, dealt round-robin, five accumulators per wave.  Every tile is
 //   formed in registers from the old S, one barrier, then all are written.
 #include "kernels.hpp"
+#include "dtype_switch.hpp"
 #include "mfma_tile.hpp"
 #include "../common.hpp"
 
@@ -256,27 +257,14 @@ static_assert(trtri_lds<double>(kTrtriMax) <= 160 * 1024, "kTrtriMax: the f64 bl
 hipError_t trtri_block(int dtype, bool lower, bool unit, i64 n, void* A, i64 lda, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > kTrtriMax || lda < n) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_trtri(lower, unit, n, static_cast<double*>(A), lda, s);
-    case ELX_F32:
-        return launch_trtri(lower, unit, n, static_cast<float*>(A), lda, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T,
+                    return launch_trtri(lower, unit, n, static_cast<T*>(A), lda, s));
 }
 
 hipError_t lauum_block(int dtype, bool lower, i64 n, void* A, i64 lda, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > kTrtriMax || lda < n) return hipErrorInvalidValue;
-    switch (dtype) {
-    case ELX_F64:
-        return launch_lauum(lower, n, static_cast<double*>(A), lda, s);
-    case ELX_F32:
-        return launch_lauum(lower, n, static_cast<float*>(A), lda, s);
-    default:
-        return hipErrorInvalidValue;
-    }
+    ELX_KERN_REAL_SWITCH(dtype, T, return launch_lauum(lower, n, static_cast<T*>(A), lda, s));
 }
 
 }  // namespace kern
