@@ -88,6 +88,7 @@ _SIGS = {
     "elx_matrix_hpd_inverse": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_lu": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _vp]),
     "elx_matrix_qr": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "elx_matrix_hermitian_tridiag": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp, _vp]),
     "elx_axpy2d": (_i, [_i, _i64, _i64, _d, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_copy2d": (_i, [_i, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "elx_pack_strided": (_i, [_i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -204,6 +205,12 @@ _SIGS = {
     "elx_least_squares": (_i, [_i, _vp, _vp, _vp]),
     "elx_qr_leaf_cols": (_i64, []),
     "elx_qr_leaf_rows": (_i64, []),
+    "elx_hermitian_tridiag": (_i, [_i, _vp, _vp]),
+    "elx_hermitian_tridiag_apply_q": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "elx_hermitian_tridiag_explicit_condensed": (_i, [_i, _vp]),
+    "elx_tridiag_panel_cols": (_i64, []),
+    "elx_set_tridiag_panel_cols": (_i, [_i64]),
+    "elx_tridiag_rows": (_i64, []),
     "elx_matrix_gemv": (_i, [_i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),
     "elx_matrix_ger": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_symv": (_i, [_i, _i, _i, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),

@@ -9,6 +9,7 @@
 #include "core/level2.hpp"
 #include "core/lu.hpp"
 #include "core/qr.hpp"
+#include "core/tridiag.hpp"
 #include "core/random.hpp"
 #include "core/io.hpp"
 #include "core/exec.hpp"
@@ -317,6 +318,23 @@ int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
         ELX_REQUIRE(tau != nullptr && sig != nullptr, "QR: null scalar or signature array");
         // the local driver on the buffer itself: launches on the stream, no read-back
         LocalQR(d, t, m, n, A, lda, tau, sig, d == Device::GPU ? DevStream(d, stream) : nullptr);
+    });
+}
+
+int elx_matrix_hermitian_tridiag(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* tau,
+                                 void* stream) {
+    return Guard([&] {
+        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "HermitianTridiag: bad UpperOrLower ", uplo);
+        ELX_REQUIRE(n >= 0, "negative HermitianTridiag dimension");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        RequireReal(t, "HermitianTridiag");
+        CheckLd(lda, n, "A");
+        if (n <= 1) return;
+        ELX_REQUIRE(A != nullptr, "HermitianTridiag: null matrix");
+        ELX_REQUIRE(tau != nullptr, "HermitianTridiag: null scalar array");
+        // the local driver on the buffer itself: launches on the stream, no read-back
+        LocalHermitianTridiag(d, t, uplo, n, A, lda, tau, d == Device::GPU ? DevStream(d, stream) : nullptr);
     });
 }
 
@@ -969,6 +987,18 @@ int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X) {
 }
 int64_t elx_qr_leaf_cols(void) { return kern::kGeqrfLeafCols; }
 int64_t elx_qr_leaf_rows(void) { return kern::kGeqrfLeafRows; }
+int elx_hermitian_tridiag(int uplo, elx_dm_t A, elx_dm_t t) {
+    return Guard([&] { HermitianTridiag(uplo, M(A), M(t)); });
+}
+int elx_hermitian_tridiag_apply_q(int side, int uplo, int orient, elx_dm_t A, elx_dm_t t, elx_dm_t B) {
+    return Guard([&] { herm_tridiag::ApplyQ(side, uplo, orient, M(A), M(t), M(B)); });
+}
+int elx_hermitian_tridiag_explicit_condensed(int uplo, elx_dm_t A) {
+    return Guard([&] { herm_tridiag::ExplicitCondensed(uplo, M(A)); });
+}
+int64_t elx_tridiag_panel_cols(void) { return TridiagPanelCols(); }
+int elx_set_tridiag_panel_cols(int64_t w) { return Guard([&] { SetTridiagPanelCols(w); }); }
+int64_t elx_tridiag_rows(void) { return kern::kSytrdRows; }
 // ---- Level 2 ----------------------------------------------------------------------
 namespace {
 void CheckInc(int64_t inc, const char* what) { ELX_REQUIRE(inc >= 1, what, " stride ", inc, " < 1"); }

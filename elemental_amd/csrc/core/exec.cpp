@@ -326,14 +326,31 @@ void QR(Device dev, DType t, Int m, Int w, void* A, Int lda, void* tau, void* si
     EXEC_REAL_SWITCH(t, T, cpu_qr_panel(m, w, static_cast<T*>(A), lda, static_cast<T*>(tau), static_cast<T*>(sig)));
 }
 
-void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s) {
+void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s,
+                 bool upper, Int off) {
     RequireReal(t, "QR");
     if (m <= 0 || nb <= 0) return;
     if (dev == Device::GPU) {
-        check(kern::qr_explicit_u((int)t, m, nb, A, lda, U, ldu, s), "qr_explicit_u");
+        check(kern::qr_explicit_u((int)t, m, nb, A, lda, U, ldu, s, upper, off), "qr_explicit_u");
         return;
     }
-    EXEC_REAL_SWITCH(t, T, cpu_qr_explicit_u(m, nb, static_cast<const T*>(A), lda, static_cast<T*>(U), ldu));
+    EXEC_REAL_SWITCH(t, T,
+                     cpu_qr_explicit_u(m, nb, static_cast<const T*>(A), lda, static_cast<T*>(U), ldu, upper, off));
+}
+
+size_t SytrdWorkBytes(Int n) { return kern::sytrd_work_bytes(n); }
+
+void SytrdPanel(DType t, bool lower, Int n, Int c0, Int w, void* A, Int lda, void* tau, void* V, void* W, Int ldv,
+                void* work, hipStream_t s) {
+    RequireReal(t, "HermitianTridiag");
+    if (n <= 1 || w <= 0) return;
+    check(kern::sytrd_panel((int)t, lower, n, c0, w, A, lda, tau, V, W, ldv, work, s), "sytrd_panel");
+}
+
+void HostHermitianTridiag(DType t, bool lower, Int n, void* A, Int lda, void* tau) {
+    RequireReal(t, "HermitianTridiag");
+    if (n <= 1) return;
+    EXEC_REAL_SWITCH(t, T, cpu_sytrd(lower, n, static_cast<T*>(A), lda, static_cast<T*>(tau)));
 }
 
 void QRFixT(Device dev, DType t, Int nb, void* S, Int lds, const void* tau, hipStream_t s) {

@@ -77,8 +77,21 @@ void Laswp(Device dev, DType t, Int m, Int n, void* A, Int lda, const int* piv, 
 size_t QRWorkBytes(Device dev, Int m);
 void QR(Device dev, DType t, Int m, Int w, void* A, Int lda, void* tau, void* sig, void* work, hipStream_t s);
 // U (m x nb) := the reflectors packed below A's diagonal, made explicit (zero
-// above the diagonal, 1 on it)
-void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s);
+// above the diagonal, 1 on it).  upper: the reflectors packed above the diagonal
+// A(off + c, c) instead (zero below it, 1 on it), as HermitianTridiag(UPPER) leaves them
+void QRExplicitU(Device dev, DType t, Int m, Int nb, const void* A, Int lda, void* U, Int ldu, hipStream_t s,
+                 bool upper = false, Int off = 0);
+// Device::GPU: one panel of the blocked tridiagonalization (kern::sytrd_panel):
+// columns c0, c0 +- 1, .. (w of them, at most kern::kSytrdMaxPanelCols) of the n x n
+// A's uplo triangle are reduced; V and W (n x w, leading dimension ldv) receive the
+// explicit reflectors and the vectors of the update owed to the trailing triangle,
+// A22 -= V W^T + W V^T.  work: SytrdWorkBytes(n) bytes.  Launches and nothing else
+size_t SytrdWorkBytes(Int n);
+void SytrdPanel(DType t, bool lower, Int n, Int c0, Int w, void* A, Int lda, void* tau, void* V, void* W, Int ldv,
+                void* work, hipStream_t s);
+// Device::CPU: the whole reduction Q^T A Q = T as the unblocked column loop
+// (herm_tridiag::LowerBlocked / UpperBlocked's sequential form), same conventions
+void HostHermitianTridiag(DType t, bool lower, Int n, void* A, Int lda, void* tau);
 // S (nb x nb) := tril(S) with diag(S) = 1 / tau (FixDiagonal, ApplyPacked/LLVF.hpp)
 void QRFixT(Device dev, DType t, Int nb, void* S, Int lds, const void* tau, hipStream_t s);
 // A(i, :) *= sig[i0 + i * is] (DiagonalScale(LEFT) by a vector of A's type and memory space)

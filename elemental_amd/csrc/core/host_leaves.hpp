@@ -1,11 +1,12 @@
 // Device::CPU, the factorisation leaves: the unblocked loops behind
-// exec::Cholesky, LU, Laswp, QR (and its three helpers), TriangularInverse
-// and Trtrmm.  f64 / f32 only, computed in the element type itself.
+// exec::Cholesky, LU, Laswp, QR (and its three helpers), HostHermitianTridiag,
+// TriangularInverse and Trtrmm.  f64 / f32 only, computed in the element type itself.
 #pragma once
 #include "../common.hpp"
 #include <algorithm>
 #include <cmath>
 #include <utility>
+#include <vector>
 
 namespace elx {
 namespace exec {
@@ -114,9 +115,71 @@ void cpu_qr_panel(Int m, Int w, S* A, Int lda, S* tau, S* sig) {
 }
 
 template <typename S>
-void cpu_qr_explicit_u(Int m, Int nb, const S* A, Int lda, S* U, Int ldu) {
+void cpu_qr_explicit_u(Int m, Int nb, const S* A, Int lda, S* U, Int ldu, bool upper, Int off) {
     for (Int c = 0; c < nb; ++c)
-        for (Int i = 0; i < m; ++i) U[i + c * ldu] = i > c ? A[i + c * lda] : (i == c ? S(1) : S(0));
+        for (Int i = 0; i < m; ++i) {
+            const Int d = off + c;
+            U[i + c * ldu] = (upper ? i < d : i > d) ? A[i + c * lda] : (i == d ? S(1) : S(0));
+        }
+}
+
+// The unblocked tridiagonalization (the sequential loop of herm_tridiag::
+// LowerBlocked / UpperBlocked) with cpu_qr_panel's reflector.  S(i,j), i >= j, is
+// A(i,j) when lower; when upper it is A(n-1-i, n-1-j): UPPER is LOWER on the
+// matrix with both index orders reversed, and tau is reversed with it.  Per
+// column k: the reflector of S(k+1:n, k) (pivot row k+1), w = t S22 v, w -=
+// (t/2)(w.v) v, S22 -= v w^T + w v^T on the stored triangle.  Sums in double
+template <typename S>
+void cpu_sytrd(bool lower, Int n, S* A, Int lda, S* tau) {
+    auto a = [&](Int i, Int j) -> S& { return lower ? A[i + j * lda] : A[(n - 1 - i) + (n - 1 - j) * lda]; };
+    std::vector<double> v(n > 0 ? n : 0), w(n > 0 ? n : 0);
+    for (Int k = 0; k + 1 < n; ++k) {
+        double mx = 0.0;
+        for (Int i = k + 2; i < n; ++i) {
+            const double x = std::fabs((double)a(i, k));
+            if (x > mx || x != x) mx = x;  // a NaN stays
+        }
+        const double alpha = (double)a(k + 1, k);
+        double beta, t;
+        if (mx == 0.0) {
+            beta = -alpha;
+            t = 2.0;
+            for (Int i = k + 2; i < n; ++i) a(i, k) = S(0);
+        } else {
+            double ssq = 0.0;
+            for (Int i = k + 2; i < n; ++i) {
+                const double r = (double)a(i, k) / mx;
+                ssq += r * r;
+            }
+            const double nrm = std::hypot(alpha, mx * std::sqrt(ssq));
+            beta = alpha <= 0.0 ? nrm : -nrm;
+            t = (double)(S)((beta - alpha) / beta);
+            const double denom = alpha - beta;
+            for (Int i = k + 2; i < n; ++i) a(i, k) = (S)((double)a(i, k) / denom);
+        }
+        v[k + 1] = 1.0;
+        for (Int i = k + 2; i < n; ++i) v[i] = (double)a(i, k);
+        for (Int i = k + 1; i < n; ++i) w[i] = 0.0;
+        for (Int j = k + 1; j < n; ++j) {
+            w[j] += (double)a(j, j) * v[j];
+            for (Int i = j + 1; i < n; ++i) {
+                const double x = (double)a(i, j);
+                w[i] += x * v[j];
+                w[j] += x * v[i];
+            }
+        }
+        double dot = 0.0;
+        for (Int i = k + 1; i < n; ++i) {
+            w[i] *= t;
+            dot += w[i] * v[i];
+        }
+        const double coef = -0.5 * t * dot;
+        for (Int i = k + 1; i < n; ++i) w[i] = (double)(S)(w[i] + coef * v[i]);
+        for (Int j = k + 1; j < n; ++j)
+            for (Int i = j; i < n; ++i) a(i, j) = (S)((double)a(i, j) - (v[i] * w[j] + w[i] * v[j]));
+        a(k + 1, k) = (S)beta;
+        tau[lower ? k : n - 2 - k] = (S)t;
+    }
 }
 
 template <typename S>

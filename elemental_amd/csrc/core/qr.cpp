@@ -78,7 +78,8 @@ struct LocalQRCall {
 // S of its UT transform, both [*,*], computed redundantly on every rank
 struct StagedPanel {
     DMPtr U, S;
-    StagedPanel(const DistMatrix& Ps, const char* tau) {
+    // upper: the reflectors lie above the diagonal Ps(off + c, c) (HermitianTridiag(UPPER))
+    StagedPanel(const DistMatrix& Ps, const char* tau, bool upper = false, Int off = 0) {
         const Int h = Ps.Height(), nb = Ps.Width();
         U = Ps.Like(Dist::STAR, Dist::STAR);
         U->Resize(h, nb);
@@ -86,7 +87,8 @@ struct StagedPanel {
         S->Resize(nb, nb);
         const Int ldu = std::max<Int>(1, U->LDim()), lds = std::max<Int>(1, S->LDim());
         hipStream_t s = U->Stream();
-        exec::QRExplicitU(Ps.Dev(), Ps.Type(), h, nb, Ps.Buffer(), std::max<Int>(1, Ps.LDim()), U->Buffer(), ldu, s);
+        exec::QRExplicitU(Ps.Dev(), Ps.Type(), h, nb, Ps.Buffer(), std::max<Int>(1, Ps.LDim()), U->Buffer(), ldu, s, upper,
+                          off);
         exec::Gemm(Ps.Dev(), Ps.Type(), true, false, nb, nb, h, 1.0, U->Buffer(), ldu, U->Buffer(), ldu, 0.0,
                    S->Buffer(), lds, s);
         exec::QRFixT(Ps.Dev(), Ps.Type(), nb, S->Buffer(), lds, tau, s);
@@ -177,6 +179,29 @@ void QR(DistMatrix& APre, DistMatrix& t, DistMatrix& d) {
     Ap.Finish();
 }
 
+// lower: Q = H_0 .. H_{k-1}, block b is P(k0:m, k0:k1) on B(k0:m, :), NORMAL runs the
+// blocks backward with S^-T.  upper: Q = H_{k-1} .. H_0, block b is P(0:k1, k0:k1)
+// on B(0:k1, :), and the product in decreasing order makes S^-1 the NORMAL one, the
+// blocks forward
+void detail::ApplyPackedReflectors(bool upper, bool normal, const DistMatrix& P, const char* tau, DistMatrix& B) {
+    const Int m = P.Height(), k = std::min(m, P.Width());
+    if (k <= 0 || B.Width() == 0) return;
+    const Int es = (Int)P.ElemSize(), nb = std::max<Int>(1, Blocksize()), nB = B.Width();
+    auto Ps = B.Like(Dist::STAR, Dist::STAR);
+    auto block = [&](Int k0) {
+        const Int k1 = std::min(k, k0 + nb);
+        const Int i0 = upper ? 0 : k0, i1 = upper ? k1 : m;
+        Copy(*DistMatrix::View(P, i0, i1, k0, k1), *Ps);
+        auto B1 = DistMatrix::View(B, i0, i1, 0, nB);
+        StagedPanel(*Ps, tau + k0 * es, upper, upper ? k0 : 0).Apply(upper ? normal : !normal, *B1);
+    };
+    if (normal != upper) {
+        for (Int k0 = (k - 1) / nb * nb; k0 >= 0; k0 -= nb) block(k0);
+    } else {
+        for (Int k0 = 0; k0 < k; k0 += nb) block(k0);
+    }
+}
+
 namespace qr {
 
 void ApplyQ(int side, int orient, const DistMatrix& A, const DistMatrix& t, const DistMatrix& d, DistMatrix& BPre) {
@@ -197,22 +222,10 @@ void ApplyQ(int side, int orient, const DistMatrix& A, const DistMatrix& t, cons
     auto tp = ReadProxy(t, B, Dist::STAR, Dist::STAR), dp = ReadProxy(d, B, Dist::STAR, Dist::STAR);
     const char* tau = static_cast<const char*>(tp->Buffer());
     const char* sig = static_cast<const char*>(dp->Buffer());
-    const Int es = (Int)A.ElemSize(), nb = std::max<Int>(1, Blocksize()), nB = B.Width();
     const bool normal = orient == ELX_NORMAL;
-    auto Ps = B.Like(Dist::STAR, Dist::STAR);
-    auto block = [&](Int k0) {
-        const Int k1 = std::min(k, k0 + nb);
-        Copy(*DistMatrix::View(A, k0, m, k0, k1), *Ps);
-        auto B1 = DistMatrix::View(B, k0, m, 0, nB);
-        StagedPanel(*Ps, tau + k0 * es).Apply(!normal, *B1);
-    };
-    if (normal) {
-        ScaleRows(B, 0, k, sig);
-        for (Int k0 = (k - 1) / nb * nb; k0 >= 0; k0 -= nb) block(k0);
-    } else {
-        for (Int k0 = 0; k0 < k; k0 += nb) block(k0);
-        ScaleRows(B, 0, k, sig);
-    }
+    if (normal) ScaleRows(B, 0, k, sig);
+    detail::ApplyPackedReflectors(false, normal, A, tau, B);
+    if (!normal) ScaleRows(B, 0, k, sig);
     Bp.Finish();
 }
 

@@ -33,6 +33,15 @@ void Explicit(DistMatrix& A, DistMatrix& R);
 // A := R, the k x n upper trapezoid
 void ExplicitTriang(DistMatrix& A);
 }  // namespace qr
+namespace detail {
+// B := Q B (normal) or Q^T B for the k = min(height, width) reflectors packed in
+// P, B [MC,MR] of P's height, tau replicated in B's memory space, blocked by
+// Blocksize() (ApplyPackedReflectors, VERTICAL).  lower: reflector c lies below
+// P(c, c), Q = H_0 .. H_{k-1} (LLVF / LLVB, what QR leaves).  upper: it lies above
+// P(c, c), Q = H_{k-1} .. H_0 (LUVF / LUVB, what HermitianTridiag(UPPER) leaves
+// in A(0:n-1, 1:n)).  No signature.  Shared by qr::ApplyQ and herm_tridiag::ApplyQ
+void ApplyPackedReflectors(bool upper, bool normal, const DistMatrix& P, const char* tau, DistMatrix& B);
+}  // namespace detail
 // X := the least-squares (NORMAL) or minimum-norm (TRANSPOSE / ADJOINT) solution
 // for the m x n A, m >= n, factored in a copy (euclidean_min/LeastSquares.cpp);
 // m < n (LQ) raises UnsupportedError

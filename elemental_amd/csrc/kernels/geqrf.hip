@@ -38,7 +38,8 @@
 //
 // Helpers of the block-reflector application (reflect/ApplyPacked/LLVF.hpp):
 //   qr_explicit_u   U := the panel's reflectors, explicit: zero above the
-//                   diagonal, 1 on it (no R entry is ever read as part of U)
+//                   diagonal, 1 on it (no R entry is ever read as part of U);
+//                   upper: the reflectors above the diagonal A(off + c, c)
 //   qr_fix_t        T := tril(T) with diag(T) = 1 / t (FixDiagonal)
 //   row_scale       A(i, :) *= sig[i0 + i * istride]
 #include "kernels.hpp"
@@ -236,11 +237,14 @@ __global__ __launch_bounds__(R) void geqrf_step_kernel(int j, int m, int w, int 
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void qr_explicit_u_kernel(i64 m, i64 nb, const T* A, i64 lda, T* U, i64 ldu) {
+__global__ __launch_bounds__(256) void qr_explicit_u_kernel(i64 m, i64 nb, const T* A, i64 lda, T* U, i64 ldu,
+                                                            bool upper, i64 off) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const i64 c = blockIdx.y;
     if (i >= m || c >= nb) return;
-    U[i + c * ldu] = i > c ? A[i + c * lda] : (i == c ? T(1) : T(0));
+    const i64 d = off + c;  // the row of the implicit 1
+    const bool packed = upper ? i < d : i > d;
+    U[i + c * ldu] = packed ? A[i + c * lda] : (i == d ? T(1) : T(0));
 }
 
 template <typename T>
@@ -287,13 +291,14 @@ hipError_t geqrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, void* tau, void
                                        s));
 }
 
-hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s) {
+hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s, bool upper,
+                         i64 off) {
     if (m <= 0 || nb <= 0) return hipSuccess;
     if (lda < m || ldu < m || nb > 65535 || m > (i64)256 * INT_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((m + 255) / 256), (unsigned)nb);
     ELX_KERN_REAL_SWITCH(dtype, T,
                     hipLaunchKernelGGL((qr_explicit_u_kernel<T>), grid, dim3(256), 0, s, m, nb,
-                                       static_cast<const T*>(A), lda, static_cast<T*>(U), ldu));
+                                       static_cast<const T*>(A), lda, static_cast<T*>(U), ldu, upper, off));
     return hipGetLastError();
 }
 

@@ -366,12 +366,29 @@ constexpr int kGeqrfLeafCols = 16, kGeqrfLeafRows = 256;
 size_t geqrf_work_bytes(i64 m);
 hipError_t geqrf_leaf(int dtype, i64 m, i64 w, void* A, i64 lda, void* tau, void* sig, void* work, hipStream_t s);
 // U (m x nb) := the reflectors packed below the diagonal of A, explicit: zero
-// above the diagonal and 1 on it
-hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s);
+// above the diagonal and 1 on it.  upper: the reflectors packed above the
+// diagonal A(off + c, c) instead (zero below it, 1 on it; ApplyPacked LUVF / LUVB)
+hipError_t qr_explicit_u(int dtype, i64 m, i64 nb, const void* A, i64 lda, void* U, i64 ldu, hipStream_t s,
+                         bool upper = false, i64 off = 0);
 // S (nb x nb) := tril(S) with diag(S) = 1 / tau (FixDiagonal of the UT transform)
 hipError_t qr_fix_t(int dtype, i64 nb, void* S, i64 lds, const void* tau, hipStream_t s);
 // A(i, :) *= sig[i0 + i * is] for the m x n A; sig has the matrix's type
 hipError_t row_scale(int dtype, i64 m, i64 n, void* A, i64 lda, const void* sig, i64 i0, i64 is, hipStream_t s);
+// One panel of the blocked tridiagonalization of the n x n symmetric A given by
+// its lower / upper triangle (sytrd.hip; LAPACK's latrd form): w <=
+// kSytrdMaxPanelCols columns from c0 on (lower: c0, c0 + 1, ..; upper: c0, c0 - 1,
+// ..), kSytrdRows rows per workgroup, five launches per column (symv's two
+// included) and one more per panel, nothing read back.  On return the columns
+// hold T's diagonal and off-diagonal and the reflectors (implicit 1 at the
+// off-diagonal row), tau[c] (lower) / tau[c - 1] (upper) the Householder scalars,
+// and V, W (n x w, leading dimension ldv, indexed by global row, the matrix's
+// type) the explicit reflectors and the vectors of the update the caller owes
+// the trailing triangle: A22 -= V W^T + W V^T.  work: sytrd_work_bytes(n) bytes
+// of device scratch.  kSytrdPanelCols is the driver's default width.  f64 / f32.
+constexpr int kSytrdRows = 256, kSytrdMaxPanelCols = 64, kSytrdPanelCols = 32;
+size_t sytrd_work_bytes(i64 n);
+hipError_t sytrd_panel(int dtype, bool lower, i64 n, i64 c0, i64 w, void* A, i64 lda, void* tau, void* V, void* W,
+                       i64 ldv, void* work, hipStream_t s);
 
 // ---- Level 2 (level2.hip): HBM-bound, no floating-point atomics, bit-reproducible.
 // Column-major A with any lda; vectors with an element stride >= 1.  Sums in

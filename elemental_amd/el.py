@@ -24,7 +24,7 @@ __all__ = [
     "Comm", "Grid", "DistMatrix", "Gemm", "LocalGemm", "Axpy", "Scale", "Zero", "Fill", "Hadamard",
     "EntrywiseMap", "Combine", "AxpyContract", "InitializeRandom", "Uniform", "Transpose", "SetBlocksize",
     "Blocksize", "PushBlocksizeStack", "PopBlocksizeStack", "EmptyBlocksizeStack", "Initialize", "Finalize",
-    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "QR", "QRApplyQ", "QRSolveAfter", "QRExplicit", "QRExplicitTriang", "LeastSquares", "Symm", "Hemm", "Gemv", "LocalGemv", "Ger", "Symv", "Hemv", "SymvLocalColAccumulate", "Syr", "Syr2", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
+    "SetComputePanel", "FrobeniusNorm", "Syrk", "Herk", "Syr2k", "Her2k", "Trrk", "Trsm", "Trmm", "Cholesky", "CholeskySolveAfter", "NonHPDMatrixError", "TriangularInverse", "Trtrmm", "HPDInverse", "Permutation", "LU", "LUSolveAfter", "LinearSolve", "SingularMatrixError", "QR", "QRApplyQ", "QRSolveAfter", "QRExplicit", "QRExplicitTriang", "LeastSquares", "HermitianTridiag", "HermitianTridiagApplyQ", "HermitianTridiagExplicitCondensed", "Symm", "Hemm", "Gemv", "LocalGemv", "Ger", "Symv", "Hemv", "SymvLocalColAccumulate", "Syr", "Syr2", "ScaleTrapezoid", "LEFT", "RIGHT", "NON_UNIT", "UNIT", "LOWER", "UPPER",
     "NORMAL", "TRANSPOSE", "ADJOINT", "MC", "MD", "MR", "VC", "VR", "STAR", "CIRC", "CPU", "GPU",
     "F32", "F64", "F16", "BF16", "GEMM_DEFAULT", "GEMM_SUMMA_A", "GEMM_SUMMA_A_MS", "GEMM_SUMMA_B",
     "GEMM_SUMMA_B_MS", "GEMM_SUMMA_C", "GEMM_SUMMA_C_MS", "GEMM_SUMMA_DOT", "GEMM_CANNON",
@@ -504,6 +504,29 @@ def QRExplicit(A: DistMatrix, R: DistMatrix):
 def QRExplicitTriang(A: DistMatrix):
     """El::qr::ExplicitTriang(A): A := R, the k x n upper trapezoid."""
     call("elx_qr_explicit_triang", A.h)
+
+
+def HermitianTridiag(uplo, A: DistMatrix):
+    """El::HermitianTridiag(uplo, A, householderScalars) (condense/HermitianTridiag.cpp):
+    Q^T A Q = T in place on A's uplo triangle (the other one is neither read nor
+    written); returns t, a [*,*] matrix of (n - 1) x 1 Householder scalars.  LOWER:
+    diag(A) and A(k+1, k) are T, A(k+2:n, k) the reflector of H_k; UPPER: A(k-1, k) is
+    the superdiagonal, A(0:k-1, k) the reflector with scalar t(k-1)."""
+    t = A.like(STAR, STAR)
+    call("elx_hermitian_tridiag", uplo, A.h, t.h)
+    return t
+
+
+def HermitianTridiagApplyQ(side, uplo, orientation, A: DistMatrix, t: DistMatrix, B: DistMatrix):
+    """El::herm_tridiag::ApplyQ(side, uplo, orientation, A, t, B): B := Q B (NORMAL) or
+    Q^T B (TRANSPOSE / ADJOINT) from what El::HermitianTridiag left in A and t.  LEFT only."""
+    call("elx_hermitian_tridiag_apply_q", side, uplo, orientation, A.h, t.h, B.h)
+
+
+def HermitianTridiagExplicitCondensed(uplo, A: DistMatrix):
+    """El::herm_tridiag::ExplicitCondensed(uplo, A): the reduction, then zero outside
+    the three diagonals on the uplo side."""
+    call("elx_hermitian_tridiag_explicit_condensed", uplo, A.h)
 
 
 def LeastSquares(orientation, A: DistMatrix, B: DistMatrix, X: DistMatrix):

@@ -1222,6 +1222,40 @@ void ExplicitTriang(AbstractDistMatrix<T>& A) {
     detail::Check(elx_qr_explicit_triang(A.h()));
 }
 }  // namespace qr
+// Q^H A Q = T in place on the uplo triangle of the square A
+// (src/lapack_like/condense/HermitianTridiag.cpp); the other triangle is neither
+// read nor written.  householderScalars is resized to (n - 1) x 1.  LOWER: diag(A)
+// and A(k+1, k) are T, A(k+2:n, k) the reflector of H_k (implicit 1 at row k+1), Q =
+// H_0 .. H_{n-2}.  UPPER: A(k-1, k) is the superdiagonal, A(0:k-1, k) the reflector
+// (implicit 1 at row k-1) with scalar k-1, Q = H_{n-1} .. H_1.  float and double
+template <typename T>
+void HermitianTridiag(UpperOrLower uplo, AbstractDistMatrix<T>& A, AbstractDistMatrix<T>& householderScalars) {
+    detail::Check(elx_hermitian_tridiag(uplo, A.h(), householderScalars.h()));
+}
+template <typename T>
+void HermitianTridiag(UpperOrLower uplo, AbstractMatrix<T>& A, AbstractMatrix<T>& householderScalars) {
+    if (householderScalars.GetDevice() != A.GetDevice())
+        throw LogicError("HermitianTridiag: A and householderScalars must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("HermitianTridiag: A must be square");
+    householderScalars.Resize(A.Height() > 0 ? A.Height() - 1 : 0, 1);
+    detail::Check(elx_matrix_hermitian_tridiag(detail::TypeCode<T>::value, static_cast<int>(A.GetDevice()), uplo,
+                                               A.Height(), A.Buffer(), A.LDim() > 1 ? A.LDim() : 1,
+                                               householderScalars.Buffer(), A.Stream()));
+}
+namespace herm_tridiag {
+// B := Q B (NORMAL) or Q^H B (ADJOINT / TRANSPOSE) from what HermitianTridiag left
+// (HermitianTridiag/ApplyQ.hpp); side must be LEFT
+template <typename T>
+void ApplyQ(LeftOrRight side, UpperOrLower uplo, Orientation orientation, const AbstractDistMatrix<T>& A,
+            const AbstractDistMatrix<T>& householderScalars, AbstractDistMatrix<T>& B) {
+    detail::Check(elx_hermitian_tridiag_apply_q(side, uplo, orientation, A.h(), householderScalars.h(), B.h()));
+}
+// A := T on the three diagonals of the uplo side, zero on the rest of that side
+template <typename T>
+void ExplicitCondensed(UpperOrLower uplo, AbstractDistMatrix<T>& A) {
+    detail::Check(elx_hermitian_tridiag_explicit_condensed(uplo, A.h()));
+}
+}  // namespace herm_tridiag
 // X := the least-squares (NORMAL) or minimum-norm (ADJOINT / TRANSPOSE) solution; A
 // (m >= n; m < n throws UnsupportedError) is factored in a copy
 // (src/lapack_like/euclidean_min/LeastSquares.cpp)

@@ -239,6 +239,16 @@ int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t 
  * synchronize: on the GPU it is launches on the stream and nothing else.  f32/f64. */
 int elx_matrix_qr(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, void* tau, void* sig,
                   void* stream);
+/* El::HermitianTridiag on Matrix<T> (src/lapack_like/condense/HermitianTridiag.cpp): Q^T A
+ * Q = T in place on the uplo triangle of the n x n A; the other triangle is neither read
+ * nor written.  tau receives n - 1 Householder scalars of the matrix's type in its memory
+ * space.  ELX_LOWER: diag(A) and A(k+1, k) are T, A(k+2:n, k) the reflector of H_k (implicit
+ * 1 at row k+1, scalar tau[k]).  ELX_UPPER: A(k-1, k) is the superdiagonal, A(0:k-1, k) the
+ * reflector (implicit 1 at row k-1, scalar tau[k-1]).  A tail that is exactly zero gives
+ * tau = 2.  No failure mode; NaN and Inf propagate.  Does NOT synchronize: on the GPU it is
+ * launches on the stream and nothing else.  f32/f64. */
+int elx_matrix_hermitian_tridiag(int dtype, int device, int uplo, int64_t n, void* A, int64_t lda, void* tau,
+                                 void* stream);
 /* ---- Level 2 on Matrix<T> (src/blas_like/level2): column-major A with any lda, vectors
  * with an element stride >= 1 (a row of a Matrix has stride ldim).  Asynchronous on the
  * stream; sums are kept in double (f64) or float (the other types) and rounded once; two
@@ -622,6 +632,25 @@ int elx_least_squares(int orient, elx_dm_t A, elx_dm_t B, elx_dm_t X);
 /* the QR leaf kernel's panel width and its rows per workgroup (kGeqrfLeafCols, kGeqrfLeafRows) */
 int64_t elx_qr_leaf_cols(void);
 int64_t elx_qr_leaf_rows(void);
+/* El::HermitianTridiag (src/lapack_like/condense/HermitianTridiag.cpp): A := the condensed
+ * form on its uplo triangle, t (any distribution) is resized to (n - 1) x 1 and receives
+ * the Householder scalars.  A grid of more than one process runs the right-looking loop over
+ * elx_blocksize on A [MC,MR]; only the last block is staged [*,*].  float and double */
+int elx_hermitian_tridiag(int uplo, elx_dm_t A, elx_dm_t t);
+/* El::herm_tridiag::ApplyQ: B := Q B (ELX_NORMAL) or Q^T B from elx_hermitian_tridiag's A
+ * and t.  side must be ELX_LEFT (ELX_ERR_LOGIC otherwise) */
+int elx_hermitian_tridiag_apply_q(int side, int uplo, int orient, elx_dm_t A, elx_dm_t t, elx_dm_t B);
+/* El::herm_tridiag::ExplicitCondensed: the reduction, then zero outside the three
+ * diagonals on the uplo side */
+int elx_hermitian_tridiag_explicit_condensed(int uplo, elx_dm_t A);
+/* the local driver's panel width (kSytrdPanelCols = 32 unless elx_set_tridiag_panel_cols
+ * changed it) and the panel kernels' rows per workgroup (kSytrdRows).  The setter takes 1 ..
+ * 64, or 0 for the default; it exists for the width measurement in tools/tridiag_bench.py.
+ * The environment variable ELX_TRIDIAG_PANEL=level2, read at every call, selects the panel
+ * composed from the Level-2 routines instead of the fused kernels (the timing baseline) */
+int64_t elx_tridiag_panel_cols(void);
+int elx_set_tridiag_panel_cols(int64_t w);
+int64_t elx_tridiag_rows(void);
 /* ---- Level 2 on DistMatrices (src/blas_like/level2).  A vector is an n x 1 or a 1 x n
  * DistMatrix of any distribution; A of another distribution than [MC,MR] goes through a
  * [MC,MR] copy.  Real types: `conjugate` is accepted and changes nothing (Hemv = Symv,
