@@ -82,6 +82,9 @@ _SIGS = {
     "elx_matrix_axpy": (_i, [_i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_copy": (_i, [_i, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "elx_matrix_trmm": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
+    "elx_matrix_trsm": (_i, [_i, _i, _i, _i, _i, _i, _i64, _i64, _d, _vp, _i64, _vp, _i64, _vp]),
+    "elx_trsm_plan": (_i, [_i, _i64, _i64, POINTER(c_int), POINTER(c_int), POINTER(c_int64)]),
+    "elx_trsm_last_launch": (_i, []),
     "elx_matrix_cholesky": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_triangular_inverse": (_i, [_i, _i, _i, _i, _i64, _vp, _i64, _vp]),
     "elx_matrix_trtrmm": (_i, [_i, _i, _i, _i64, _vp, _i64, _vp]),

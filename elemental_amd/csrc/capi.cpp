@@ -279,6 +279,48 @@ int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int d
         exec::Copy2DBatch(d, t, &back, 1, false, 0.0, s);
     });
 }
+int elx_matrix_trsm(int dtype, int device, int side, int uplo, int orient, int diag, int64_t m, int64_t n, double alpha,
+                    const void* A, int64_t lda, void* B, int64_t ldb, void* stream) {
+    return Guard([&] {
+        CheckOp(orient);
+        ELX_REQUIRE(side == ELX_LEFT || side == ELX_RIGHT, "Trsm: bad LeftOrRight ", side);
+        ELX_REQUIRE(uplo == ELX_LOWER || uplo == ELX_UPPER, "Trsm: bad UpperOrLower ", uplo);
+        ELX_REQUIRE(diag == ELX_NON_UNIT || diag == ELX_UNIT, "Trsm: bad UnitOrNonUnit ", diag);
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative Trsm dimension");
+        const bool left = side == ELX_LEFT;
+        CheckLd(lda, left ? m : n, "A");
+        CheckLd(ldb, m, "B");
+        const Device d = ToDevice(device);
+        const DType t = ToDType(dtype);
+        RequireReal(t, "Trsm");
+        if (m == 0 || n == 0) return;
+        hipStream_t s = DevStream(d, stream);
+        const bool lower = uplo == ELX_LOWER, trans = orient != ELX_NORMAL, unit = diag == ELX_UNIT;
+        // B *= alpha first (Trsm.cpp:155 does the same on DistMatrices)
+        if (alpha == 0.0) return exec::Fill(d, t, m, n, 0.0, B, ldb, s);
+        if (alpha != 1.0) exec::Scale(d, t, m, n, alpha, B, ldb, s);
+        if (left) return exec::Trsm(d, t, lower, trans, unit, m, n, A, lda, B, ldb, s);
+        // X op(A) = B  <=>  op(A)^T X^T = B^T through the strided-copy (transpose) kernel
+        Buffer Bt(d, (size_t)m * n * DTypeSize(t), s);
+        const kern::Copy2D to{n, m, B, ldb, 1, Bt.data(), 1, n};
+        exec::Copy2DBatch(d, t, &to, 1, false, 0.0, s);
+        exec::Trsm(d, t, lower, !trans, unit, n, m, A, lda, Bt.data(), n, s);
+        const kern::Copy2D back{m, n, Bt.data(), n, 1, B, 1, ldb};
+        exec::Copy2DBatch(d, t, &back, 1, false, 0.0, s);
+    });
+}
+int elx_trsm_plan(int dtype, int64_t m, int64_t n, int* invert, int* lds, int64_t* lds_bytes) {
+    return Guard([&] {
+        const DType t = ToDType(dtype);
+        RequireReal(t, "Trsm");
+        ELX_REQUIRE(m >= 0 && n >= 0, "negative Trsm dimension");
+        const kern::TrsmPlan p = kern::trsm_plan(DTypeSize(t), m, n);
+        if (invert) *invert = p.invert;
+        if (lds) *lds = p.lds;
+        if (lds_bytes) *lds_bytes = (int64_t)p.lds_bytes;
+    });
+}
+int elx_trsm_last_launch(void) { return kern::trsm_last_launch(); }
 
 int elx_matrix_lu(int dtype, int device, int64_t m, int64_t n, void* A, int64_t lda, int32_t* piv, void* stream) {
     return Guard([&] {

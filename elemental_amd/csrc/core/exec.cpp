@@ -238,7 +238,7 @@ void Trsm(Device dev, DType t, bool lower, bool trans, bool unit, Int m, Int n, 
     if (m <= 0 || n <= 0) return;
     if (dev == Device::GPU) {
         const size_t es = DTypeSize(t);
-        if (m <= 256 && n >= 4 * m) {
+        if (kern::trsm_plan(es, m, n).invert) {
             // many right-hand sides: W = op(A)^-1 (m lanes of substitution), then
             // B := W B as one MFMA GEMM through a workspace (the inverted-diagonal-
             // block scheme of vendor trsm), instead of n/64 waves each running an

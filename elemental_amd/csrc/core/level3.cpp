@@ -214,9 +214,9 @@ void TrsmLeft(int uplo, int orient, bool unit, const DistMatrix& APre, DistMatri
     Buffer winv;
     auto batch_ok = [&](Int b) {
         return X.Dev() == Device::GPU && SameLocalLayout(A, Dist::STAR, Dist::STAR, 0, 0) &&
-               b * 65 * (Int)es <= kern::kTriInverseLdsMax && (m + b - 1) / b <= 65535 &&
-               kern::tri_inverse_lds_ok(static_cast<int>(X.Type()), b) &&
-               SameLocalLayout(X, Dist::STAR, Dist::VR, 0, X.RowAlign()) && X.LocalWidth() >= 4 * b;
+               SameLocalLayout(X, Dist::STAR, Dist::VR, 0, X.RowAlign()) &&
+               kern::trsm_batched_ok(es, b, m, X.LocalWidth()) &&
+               kern::tri_inverse_lds_ok(static_cast<int>(X.Type()), b);
     };
     // Batched path with the default Blocksize (128) and a large system: 256-row
     // diagonal blocks, so every leaf (inverse applied as a GEMM) and the lowest

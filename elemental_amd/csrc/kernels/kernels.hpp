@@ -288,6 +288,30 @@ constexpr long kTriInverseLdsMax = 150 * 1024;
 bool tri_inverse_lds_ok(int dtype, i64 nb);
 hipError_t tri_inverse_batched(int dtype, bool lower, bool trans, bool unit, i64 nb, i64 m, const void* A, i64 lda,
                                void* W, hipStream_t s);
+// Which local Trsm path an m x m triangle with n right-hand sides of es-byte
+// elements takes.  invert (exec::Trsm): few enough rows and many enough
+// right-hand sides that op(A)^-1 (trsm_local with ident) applied as one GEMM
+// beats n/64 waves of substitution.  lds (launch_trsm): a wave's 64 columns and
+// one column of op(A), m x 65 elements, are held in LDS (f64 m <= 129, f32 m <=
+// 259); otherwise the same loop runs on global memory.  Here (and constexpr, so
+// the code and tests/cpp/test_trsm_plan.cpp share it) as trmm_krange is.
+constexpr i64 kTrsmInvertMaxRows = 256;
+constexpr long kTrsmLdsMax = 66 * 1024;
+struct TrsmPlan { bool invert; bool lds; size_t lds_bytes; };
+constexpr TrsmPlan trsm_plan(size_t es, i64 m, i64 n) {
+    const size_t bytes = (size_t)m * 65 * es;
+    return TrsmPlan{m <= kTrsmInvertMaxRows && n >= 4 * m, bytes <= (size_t)kTrsmLdsMax, bytes};
+}
+// The arithmetic part of TrsmLeft's choice of the batched path (every nb x nb
+// diagonal block inverted by one tri_inverse_batched launch): the block fits the
+// kernel's LDS, the block count fits gridDim.y, and the local right-hand sides
+// are wide enough for the GEMMs to pay.  The layout tests and tri_inverse_lds_ok
+// stay with the caller.
+constexpr bool trsm_batched_ok(size_t es, i64 nb, i64 m, i64 local_width) {
+    return nb * 65 * (i64)es <= kTriInverseLdsMax && (m + nb - 1) / nb <= 65535 && local_width >= 4 * nb;
+}
+// what the last trsm_local launch of this process ran: 1 (ident) | 2 (LDS kernel); -1 before any (tests)
+int trsm_last_launch();
 // C := alpha * op(tri(A)) * B.  A is m x m, only its uplo triangle is read
 // (unit: the diagonal is not read either and counts as 1).  B and C are m x n,
 // C must not overlap B.  f64 / f32.

@@ -15,12 +15,15 @@
 #include "kernels.hpp"
 #include "dtype_switch.hpp"
 #include "../common.hpp"
+#include <atomic>
 
 namespace elx {
 namespace kern {
 namespace {
 
 constexpr int WAVE = 64;
+static_assert(WAVE + 1 == 65, "trsm_plan (kernels.hpp) sizes the LDS as m x 65 elements");
+std::atomic<int> g_last_launch{-1};  // trsm_last_launch()
 
 // IDENT: the right-hand sides are the identity (B is output only): B := op(A)^-1
 template <typename T, bool LDS, bool IDENT>
@@ -98,8 +101,10 @@ template <typename T>
 hipError_t launch_trsm(bool ident, bool lower, bool trans, bool unit, i64 m, i64 n, const T* A, i64 lda, T* B,
                        i64 ldb, hipStream_t s) {
     const dim3 grid((unsigned)((n + WAVE - 1) / WAVE));
-    const size_t lds = (size_t)m * (WAVE + 1) * sizeof(T);
-    if (lds <= 66 * 1024) {
+    const TrsmPlan plan = trsm_plan(sizeof(T), m, n);
+    const size_t lds = plan.lds_bytes;
+    g_last_launch.store((ident ? 1 : 0) | (plan.lds ? 2 : 0), std::memory_order_relaxed);
+    if (plan.lds) {
         if (ident)
             hipLaunchKernelGGL((trsm_kernel<T, true, true>), grid, dim3(WAVE), lds, s, lower, trans, unit, m, n, A, lda, B, ldb);
         else
@@ -159,6 +164,8 @@ hipError_t tri_inverse_batched(int dtype, bool lower, bool trans, bool unit, i64
                     return launch_tri_inverse_batched(lower, trans, unit, nb, m, static_cast<const T*>(A), lda,
                                                       static_cast<T*>(W), s));
 }
+
+int trsm_last_launch() { return g_last_launch.load(std::memory_order_relaxed); }
 
 hipError_t trsm_local(int dtype, bool ident, bool lower, bool trans, bool unit, i64 m, i64 n, const void* A, i64 lda,
                       void* B, i64 ldb, hipStream_t s) {

@@ -987,6 +987,34 @@ void Trsm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNo
     detail::Check(elx_trsm(side, uplo, orientation, diag, detail::ToDouble(alpha), A.h(), B.h(),
                            checkIfSingular ? 1 : 0));
 }
+// on local matrices (Trsm.cpp:80-127): the substitution / inverse-and-GEMM kernels
+// on the GPU (on B's stream), the library's host loop on the CPU.  float and double
+template <typename T>
+void Trsm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+          const AbstractMatrix<T>& A, AbstractMatrix<T>& B, bool checkIfSingular = false) {
+    if (A.GetDevice() != B.GetDevice()) throw LogicError("Trsm: A and B must be on the same device");
+    if (A.Height() != A.Width()) throw LogicError("Triangular matrix must be square");
+    if (A.Height() != (side == LEFT ? B.Height() : B.Width())) throw LogicError("Nonconformal Trsm");
+    detail::LocalFence<T> fence(B, {&A});
+    if (checkIfSingular && diag != UNIT)  // Trsm.cpp:62-68; on the GPU one synchronizing transfer per entry
+        for (Int i = 0; i < A.Height(); ++i) {
+            T v;
+            if (A.GetDevice() == Device::GPU)
+                detail::Check(elx_memcpy_d2h(&v, A.LockedBuffer() + i + i * A.LDim(), sizeof(T), B.Stream()));
+            else
+                v = A.LockedBuffer()[i + i * A.LDim()];
+            if (v == T(0)) throw SingularMatrixException();
+        }
+    detail::Check(elx_matrix_trsm(detail::TypeCode<T>::value, static_cast<int>(B.GetDevice()), side, uplo, orientation,
+                                  diag, B.Height(), B.Width(), detail::ToDouble(alpha), A.LockedBuffer(), A.LDim(),
+                                  B.Buffer(), B.LDim(), B.Stream()));
+}
+template <typename T, Device D>
+void Trsm(LeftOrRight side, UpperOrLower uplo, Orientation orientation, UnitOrNonUnit diag, T alpha,
+          const Matrix<T, D>& A, Matrix<T, D>& B, bool checkIfSingular = false) {
+    Trsm(side, uplo, orientation, diag, alpha, static_cast<const AbstractMatrix<T>&>(A),
+         static_cast<AbstractMatrix<T>&>(B), checkIfSingular);
+}
 // Trmm (src/blas_like/level3/Trmm.cpp): B := alpha op(tri(A)) B (LEFT) or alpha B
 // op(tri(A)) (RIGHT) in place; only A's uplo triangle is read.  float and double.
 // On local matrices (Trmm.cpp:23-51): the triangle-aware MFMA kernel on the GPU

@@ -203,6 +203,19 @@ int elx_matrix_copy(int dtype, int device, int64_t m, int64_t n, const void* A, 
 int elx_matrix_trmm(int dtype, int device, int side, int uplo, int orient, int diag,
                     int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
                     void* B, int64_t ldb, void* stream);
+/* El::Trsm on Matrix<T> (src/blas_like/level3/Trsm.cpp:80-127): B (m x n) := alpha
+ * op(tri(A))^-1 B (LEFT, A m x m) or alpha B op(tri(A))^-1 (RIGHT, A n x n), in place;
+ * only A's uplo triangle is read (and no diagonal when UNIT).  f32/f64. */
+int elx_matrix_trsm(int dtype, int device, int side, int uplo, int orient, int diag,
+                    int64_t m, int64_t n, double alpha, const void* A, int64_t lda,
+                    void* B, int64_t ldb, void* stream);
+/* The GPU path of a LEFT solve with an m x m triangle and n right-hand sides:
+ * *invert (the block is inverted and applied as one GEMM, else substitution),
+ * *lds (the kernel keeps the right-hand sides in LDS, else in global memory) and
+ * the LDS bytes of that launch.  elx_trsm_last_launch: what the last local solve of
+ * this process launched, 1 (inverse) | 2 (LDS kernel), -1 before any.  For tests. */
+int elx_trsm_plan(int dtype, int64_t m, int64_t n, int* invert, int* lds, int64_t* lds_bytes);
+int elx_trsm_last_launch(void);
 /* El::Cholesky on Matrix<T> (src/lapack_like/factor/Cholesky.cpp): the n x n A :=
  * its Cholesky factor, in place on the uplo triangle (A = L L^T for ELX_LOWER, U^T U
  * for ELX_UPPER); the other triangle is neither read nor written.  Runs the blocked

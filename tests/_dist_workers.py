@@ -289,6 +289,15 @@ def trsm_worker(rank: int, world: int, port: int, height: int, device: int, dtyp
                         assert np.isfinite(got).all() and num <= 10 * den, \
                             (f"Trsm side {side} uplo {uplo} orient {orient} diag {diag} {m}x{n} nb {nb} "
                              f"grid {r}x{c} rank {rank}: {num / den:.3g}")
+                        # column by column (this rank's rows of it against the whole column's norm):
+                        # one wrong column cannot hide in the norm of the rest
+                        if got.size:
+                            cn = np.ascontiguousarray(np.broadcast_to(np.linalg.norm(ref, axis=0), ref.shape))
+                            cden = oracle.local_block(cn, el.MC, el.MR, r, c, g.vc_rank)[0] * k * _tol(dtype)
+                            worst = float((np.linalg.norm(got - want, axis=0) / cden).max())
+                            assert worst <= 1, \
+                                (f"Trsm side {side} uplo {uplo} orient {orient} diag {diag} {m}x{n} nb {nb} "
+                                 f"grid {r}x{c} rank {rank}: column error {worst:.3g} k eps ||column||")
         finish()
     except Exception:
         traceback.print_exc()

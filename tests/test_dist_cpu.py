@@ -153,6 +153,15 @@ def test_trsm(world, height, flat, monkeypatch):
     _spawn(W.trsm_worker, world, height, el.CPU, el.F64, 19, 13, 4, 31)
 
 
+@pytest.mark.parametrize("world,height,dtype", [(1, 1, el.F64), (2, 1, el.F64), (1, 1, el.F32)])
+def test_trsm_wide(world, height, dtype):
+    """The shapes and types test_gpu_trsm adds to the distributed worker, (45, 160)
+    and f32 (45, 23) at nb = 16, here on Device::CPU: the worker's per-column bound
+    holds for plain substitution."""
+    m, n = (45, 160) if dtype == el.F64 else (45, 23)
+    _spawn(W.trsm_worker, world, height, el.CPU, dtype, m, n, 16, 47 if dtype == el.F64 else 43)
+
+
 @pytest.mark.parametrize("world,height", [(1, 1), (2, 1), (4, 2)])
 def test_symm_hemm(world, height):
     """El::Symm / El::Hemm, LEFT/RIGHT x LOWER/UPPER; A's other triangle is NaN."""
