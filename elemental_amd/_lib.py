@@ -74,6 +74,7 @@ _SIGS = {
     "elx_memcpy_d2d": (_i, [_vp, _vp, c_size_t, _vp]),
     "elx_gemm_f64": (_i, [_i, _i, _i64, _i64, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),
     "elx_gemm_f32": (_i, [_i, _i, _i64, _i64, _i64, c_float, _vp, _i64, _vp, _i64, c_float, _vp, _i64, _vp]),
+    "elx_gemm_last_levels": (_i, []),
     "elx_gemm_f16": (_i, [_i, _i, _i64, _i64, _i64, c_float, _vp, _i64, _vp, _i64, c_float, _vp, _i64, _vp]),
     "elx_gemm_bf16": (_i, [_i, _i, _i64, _i64, _i64, c_float, _vp, _i64, _vp, _i64, c_float, _vp, _i64, _vp]),
     "elx_matrix_gemm": (_i, [_i, _i, _i, _i, _i64, _i64, _i64, _d, _vp, _i64, _vp, _i64, _d, _vp, _i64, _vp]),

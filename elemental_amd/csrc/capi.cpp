@@ -184,6 +184,7 @@ ELX_GEMM_ENTRY(elx_gemm_f32, DType::F32, float, float)
 ELX_GEMM_ENTRY(elx_gemm_f16, DType::F16, uint16_t, float)
 ELX_GEMM_ENTRY(elx_gemm_bf16, DType::BF16, uint16_t, float)
 #undef ELX_GEMM_ENTRY
+int elx_gemm_last_levels(void) { return exec::GemmLastLevels(); }
 
 // ---- El::Matrix<T,D> (either device) ------------------------------------------
 namespace {

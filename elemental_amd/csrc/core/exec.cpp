@@ -2,6 +2,7 @@
 // loops themselves live in host_elem.hpp, host_blas.hpp and host_leaves.hpp.
 #include <cstdlib>
 #include "exec.hpp"
+#include "strassen.hpp"
 #include "host_blas.hpp"
 #include "host_leaves.hpp"
 #include <cmath>
@@ -80,8 +81,57 @@ void Convert2D(Device dev, DType src_t, DType dst_t, const Copy2D& d, hipStream_
     EXEC_SWITCH(src_t, TS, EXEC_SWITCH(dst_t, TD, cpu_convert<TS, TD>(d)));
 }
 
+namespace {
+thread_local int t_gemm_levels = 0;
+}
+int GemmLastLevels() { return t_gemm_levels; }
+
 void Gemm(Device dev, DType t, bool ta, bool tb, Int m, Int n, Int k, double alpha, const void* A, Int lda,
           const void* B, Int ldb, double beta, void* C, Int ldc, hipStream_t s) {
+    t_gemm_levels = 0;
+    if (m <= 0 || n <= 0) return;
+    // the knobs are read per call (two getenv), and only for the types that can take the path
+    if (k >= 2 && (t == DType::F64 || t == DType::F32)) {
+        const strassen::Knobs kn = strassen::ReadKnobs();
+        t_gemm_levels = strassen::Gemm(kn.levels, kn, dev, t, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, s);
+        if (t_gemm_levels > 0) return;
+    }
+    GemmPlain(dev, t, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, s);
+}
+
+void QuadSum(Device dev, DType t, const kern::QuadSum* q, int nq, hipStream_t s) {
+    RequireReal(t, "QuadSum");
+    if (dev == Device::GPU) { check(kern::quad_sum((int)t, q, nq, s), "quad_sum"); return; }
+    for (int d = 0; d < nq; ++d)
+        EXEC_REAL_SWITCH(t, T, {
+            const kern::QuadSum& a = q[d];
+            const T* x = static_cast<const T*>(a.x);
+            const T* y = static_cast<const T*>(a.y);
+            T* o = static_cast<T*>(a.d);
+            for (Int j = 0; j < a.n; ++j)
+                for (Int i = 0; i < a.m; ++i) o[i + j * a.ldd] = x[i + j * a.ldx] + (T)a.sy * y[i + j * a.ldy];
+        });
+}
+
+void QuadScatter(Device dev, DType t, const kern::QuadScatter& q, hipStream_t s) {
+    RequireReal(t, "QuadScatter");
+    if (dev == Device::GPU) { check(kern::quad_scatter((int)t, q, s), "quad_scatter"); return; }
+    EXEC_REAL_SWITCH(t, T, {
+        const T* M = static_cast<const T*>(q.M);
+        for (int w = 0; w < q.nt; ++w) {
+            T* c = static_cast<T*>(q.c[w]);
+            for (Int j = 0; j < q.n; ++j)
+                for (Int i = 0; i < q.m; ++i) {
+                    T v = (T)q.coef[w] * M[i + j * q.ldm];
+                    if (q.beta[w] != 0.0) v = v + (T)q.beta[w] * c[i + j * q.ldc[w]];
+                    c[i + j * q.ldc[w]] = v;
+                }
+        }
+    });
+}
+
+void GemmPlain(Device dev, DType t, bool ta, bool tb, Int m, Int n, Int k, double alpha, const void* A, Int lda,
+               const void* B, Int ldb, double beta, void* C, Int ldc, hipStream_t s) {
     if (m <= 0 || n <= 0) return;
     if (dev == Device::GPU) {
         hipError_t e = hipSuccess;

@@ -582,6 +582,104 @@ __global__ __launch_bounds__(NT) void trapezoid_kernel(bool lower, i64 m, i64 n,
     });
 }
 
+// The additions of one Strassen-Winograd level (core/strassen.cpp), on quadrant
+// views (pointer + ld).  Pre-sum: D := X + sy Y for up to two descriptors
+// (gridDim.z), 3 elements of traffic each; D may be X or Y (every element is
+// read before its own write).
+struct QuadSumBatch {
+    QuadSum q[2];
+};
+
+template <typename T>
+__global__ __launch_bounds__(NT) void quad_sum_kernel(QuadSumBatch b, bool vec) {
+    using E = Elem<T>;
+    using S = typename E::storage;
+    const QuadSum& q = b.q[blockIdx.z];
+    const auto sy = (typename E::compute)q.sy;
+    S* const p[3] = {static_cast<S*>(q.d), const_cast<S*>(static_cast<const S*>(q.x)),
+                     const_cast<S*>(static_cast<const S*>(q.y))};
+    const i64 l[3] = {q.ldd, q.ldx, q.ldy};
+    ew_2d<S, 3, false>(q.m, q.n, p, l, vec, [&](const S(&x)[3]) { return E::store(E::load(x[1]) + sy * E::load(x[2])); });
+}
+
+// Scatter: C_t := beta_t C_t + coef_t M for the nt <= 2 targets in one pass over
+// M: M is read once, each target written once and read only where its beta is
+// not 0 (1 + sum (1 + [beta_t != 0]) elements of traffic).  Same sweep as ew_2d:
+// columns over gridDim.y, a workgroup per CHUNK of a column, UNROLL 16-B
+// vectors per operand in flight per lane.
+template <typename T>
+__global__ __launch_bounds__(NT) void quad_scatter_kernel(QuadScatter q, bool vec) {
+    using E = Elem<T>;
+    using S = typename E::storage;
+    using Cm = typename E::compute;
+    constexpr int N = V16<S>::N;
+    constexpr i64 CHUNK = (i64)NT * UNROLL * N;
+    const S* M = static_cast<const S*>(q.M);
+    S* const c0p = static_cast<S*>(q.c[0]);
+    S* const c1p = static_cast<S*>(q.c[1]);
+    const bool two = q.nt > 1;
+    const bool rd0 = q.beta[0] != 0.0, rd1 = two && q.beta[1] != 0.0;
+    const Cm b0 = (Cm)q.beta[0], b1 = (Cm)q.beta[1], a0 = (Cm)q.coef[0], a1 = (Cm)q.coef[1];
+    auto out = [](Cm a, S mv, bool rd, Cm b, S cv) {
+        Cm v = a * E::load(mv);
+        if (rd) v = v + b * E::load(cv);
+        return E::store(v);
+    };
+    for (i64 j = blockIdx.y; j < q.n; j += gridDim.y) {
+        const S* mc = M + j * q.ldm;
+        S* y0 = c0p + j * q.ldc[0];
+        S* y1 = two ? c1p + j * q.ldc[1] : nullptr;
+        for (i64 c0 = (i64)blockIdx.x * CHUNK; c0 < q.m; c0 += (i64)gridDim.x * CHUNK) {
+            if (vec && c0 + CHUNK <= q.m) {
+                V16<S> x[UNROLL], u0[UNROLL] = {}, u1[UNROLL] = {};
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const i64 i = c0 + (u * NT + threadIdx.x) * N;
+                    x[u] = *reinterpret_cast<const V16<S>*>(mc + i);
+                    if (rd0) u0[u] = *reinterpret_cast<const V16<S>*>(y0 + i);
+                    if (rd1) u1[u] = *reinterpret_cast<const V16<S>*>(y1 + i);
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const i64 i = c0 + (u * NT + threadIdx.x) * N;
+#pragma unroll
+                    for (int e = 0; e < N; ++e) u0[u].v[e] = out(a0, x[u].v[e], rd0, b0, u0[u].v[e]);
+                    *reinterpret_cast<V16<S>*>(y0 + i) = u0[u];
+                    if (two) {
+#pragma unroll
+                        for (int e = 0; e < N; ++e) u1[u].v[e] = out(a1, x[u].v[e], rd1, b1, u1[u].v[e]);
+                        *reinterpret_cast<V16<S>*>(y1 + i) = u1[u];
+                    }
+                }
+            } else {
+                const i64 end = c0 + CHUNK < q.m ? c0 + CHUNK : q.m;
+                for (i64 i = c0 + (i64)threadIdx.x * N; i < end; i += (i64)NT * N) {
+                    if (vec && i + N <= end) {
+                        const V16<S> x = *reinterpret_cast<const V16<S>*>(mc + i);
+                        V16<S> u0 = {}, u1 = {};
+                        if (rd0) u0 = *reinterpret_cast<const V16<S>*>(y0 + i);
+                        if (rd1) u1 = *reinterpret_cast<const V16<S>*>(y1 + i);
+#pragma unroll
+                        for (int e = 0; e < N; ++e) u0.v[e] = out(a0, x.v[e], rd0, b0, u0.v[e]);
+                        *reinterpret_cast<V16<S>*>(y0 + i) = u0;
+                        if (two) {
+#pragma unroll
+                            for (int e = 0; e < N; ++e) u1.v[e] = out(a1, x.v[e], rd1, b1, u1.v[e]);
+                            *reinterpret_cast<V16<S>*>(y1 + i) = u1;
+                        }
+                    } else {
+                        for (i64 e = i; e < i + N && e < end; ++e) {
+                            const S mv = mc[e];
+                            y0[e] = out(a0, mv, rd0, b0, rd0 ? y0[e] : S{});
+                            if (two) y1[e] = out(a1, mv, rd1, b1, rd1 ? y1[e] : S{});
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // Launch geometry of ew_2d: collapse to one column when every operand is
 // contiguous (ld == m), and decide the 16-B vector path.
 struct EwShape {
@@ -865,6 +963,52 @@ hipError_t trapezoid2d(int dtype, bool lower, i64 m, i64 n, double alpha, const 
         hipLaunchKernelGGL((trapezoid_kernel<T>), grid2d(m, n), dim3(NT), 0, s, lower, m, n, alpha,
                            static_cast<const typename Elem<T>::storage*>(X), ldx, beta,
                            static_cast<typename Elem<T>::storage*>(Y), ldy, i0, istride, j0, jstride, offset));
+    return hipGetLastError();
+}
+
+namespace {
+// one workgroup per CHUNK of a column, as ew_shape without the collapse (a
+// quadrant view is never contiguous); the kernels' loops cover a clipped grid
+template <typename S>
+dim3 quad_grid(i64 m, i64 n, int nz) {
+    constexpr i64 chunk = (i64)NT * UNROLL * (16 / sizeof(S));
+    const i64 gx = std::max<i64>(1, std::min<i64>((m + chunk - 1) / chunk, (1ll << 31) - 1));
+    return dim3((unsigned)gx, (unsigned)std::max<i64>(1, std::min<i64>(n, 65535)), (unsigned)nz);
+}
+bool quad_al16(const void* p, i64 ld, i64 n, int es) {
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (n == 1 || (ld * es) % 16 == 0);
+}
+}  // namespace
+
+hipError_t quad_sum(int dtype, const QuadSum* q, int nq, hipStream_t s) {
+    if (nq < 1 || nq > 2) return hipErrorInvalidValue;
+    const int es = dtype_size(dtype);
+    QuadSumBatch b{};
+    i64 m = 0, n = 0;
+    int used = 0;
+    bool vec = true;
+    for (int i = 0; i < nq; ++i) {
+        if (q[i].m <= 0 || q[i].n <= 0) continue;
+        b.q[used++] = q[i];
+        m = std::max(m, q[i].m);
+        n = std::max(n, q[i].n);
+        vec = vec && quad_al16(q[i].d, q[i].ldd, q[i].n, es) && quad_al16(q[i].x, q[i].ldx, q[i].n, es) &&
+              quad_al16(q[i].y, q[i].ldy, q[i].n, es);
+    }
+    if (used == 0) return hipSuccess;
+    ELX_KERN_REAL_SWITCH(dtype, T,
+        hipLaunchKernelGGL((quad_sum_kernel<T>), quad_grid<T>(m, n, used), dim3(NT), 0, s, b, vec));
+    return hipGetLastError();
+}
+
+hipError_t quad_scatter(int dtype, const QuadScatter& q, hipStream_t s) {
+    if (q.nt < 1 || q.nt > 2) return hipErrorInvalidValue;
+    if (q.m <= 0 || q.n <= 0) return hipSuccess;
+    const int es = dtype_size(dtype);
+    bool vec = quad_al16(q.M, q.ldm, q.n, es);
+    for (int t = 0; t < q.nt; ++t) vec = vec && quad_al16(q.c[t], q.ldc[t], q.n, es);
+    ELX_KERN_REAL_SWITCH(dtype, T,
+        hipLaunchKernelGGL((quad_scatter_kernel<T>), quad_grid<T>(q.m, q.n, 1), dim3(NT), 0, s, q, vec));
     return hipGetLastError();
 }
 

@@ -254,6 +254,32 @@ struct ContractSum {
 };
 hipError_t contract_sum(int dtype, const ContractSum& c, double alpha, hipStream_t s, int max_wgs = 0);
 
+// The additions of a Strassen-Winograd level (core/strassen.cpp) on column-major
+// quadrant views, any m, n and ld; f64 / f32.  16-B accesses when every pointer
+// and column start of the launch is 16-B aligned, element by element otherwise.
+//   quad_sum      D := X + sy Y for nq <= 2 descriptors in one launch (the S
+//                 and the T of one product); D may be X or Y.  3 elements of
+//                 traffic per element of D.
+//   quad_scatter  C_t := beta_t C_t + coef_t M for nt <= 2 targets in one pass
+//                 over M.  A target whose beta is 0 is not read.  1 + sum_t (1 +
+//                 [beta_t != 0]) elements of traffic per element of M.
+struct QuadSum {
+    i64 m, n;
+    void* d; i64 ldd;
+    const void* x; i64 ldx;
+    const void* y; i64 ldy;
+    double sy;
+};
+struct QuadScatter {
+    i64 m, n;
+    const void* M; i64 ldm;
+    int nt;
+    void* c[2]; i64 ldc[2];
+    double beta[2], coef[2];
+};
+hipError_t quad_sum(int dtype, const QuadSum* q, int nq, hipStream_t s);
+hipError_t quad_scatter(int dtype, const QuadScatter& q, hipStream_t s);
+
 // Type-converting strided copy: dst(i,j) = (dst type) src(i,j), one rounding (elem.hpp).
 hipError_t convert2d(int src_dtype, int dst_dtype, const Copy2D& d, hipStream_t s);
 hipError_t fill2d(int dtype, i64 m, i64 n, double v, void* A, i64 lda, hipStream_t s);
