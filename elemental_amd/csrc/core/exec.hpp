@@ -22,8 +22,8 @@ void ContractSum(Device dev, DType t, Int m, Int n, void* dst, Int dcs, Int drs,
                  int nsrc, double alpha, hipStream_t s);
 // dst(i,j) = (dst type) src(i,j): Copy_GPU_impl<SrcT,DestT> (Copy.cu:93-205)
 void Convert2D(Device dev, DType src_t, DType dst_t, const Copy2D& d, hipStream_t s);
-// C := alpha op(A) op(B) + beta C.  Large f64 / f32 products take one level of
-// Strassen-Winograd over GemmPlain (strassen.hpp says which); GemmLastLevels: how
+// C := alpha op(A) op(B) + beta C.  Large f64 / f32 products take one or two levels
+// of Strassen-Winograd over GemmPlain (strassen.hpp says which); GemmLastLevels: how
 // many levels the last Gemm of this thread used (0: the plain kernel)
 void Gemm(Device dev, DType t, bool ta, bool tb, Int m, Int n, Int k, double alpha,
           const void* A, Int lda, const void* B, Int ldb, double beta, void* C, Int ldc, hipStream_t s);

@@ -12,7 +12,9 @@
 // feed one quadrant each and go straight into it.  beta is applied at the first
 // write of each quadrant; with beta = 0 no quadrant of C is read before it has
 // been written.  Per element of a quadrant the additions move 4 x 6 (sums) + 5
-// + 3 + 3 + 5 (scatters) = 40 elements.
+// + 3 + 3 + 5 (scatters) = 40 elements.  A sub-product that passes the inner
+// threshold (Knobs::min2) runs the same schedule one level down, with S, T and M
+// of its own.
 #include "strassen.hpp"
 #include "exec.hpp"
 #include <cstdlib>
@@ -21,12 +23,15 @@ namespace elx {
 namespace strassen {
 
 Knobs ReadKnobs() {
-    Knobs kn{1, kDefaultMin, false};
-    if (const char* v = getenv("ELX_GEMM_STRASSEN")) kn.levels = std::max(0, std::min(2, atoi(v)));
+    Knobs kn{2, kDefaultMin, kDefaultMin2, false};
+    const char* lv = getenv("ELX_GEMM_STRASSEN");
+    if (lv) kn.levels = std::max(0, std::min(2, atoi(lv)));
     if (const char* v = getenv("ELX_GEMM_STRASSEN_MIN")) {
         kn.min = std::max<Int>(2, atoll(v));
         kn.forced = true;
+        if (lv) kn.min2 = kn.min;  // two levels asked for by name: both under the one threshold
     }
+    if (const char* v = getenv("ELX_GEMM_STRASSEN_MIN2")) kn.min2 = std::max<Int>(2, atoll(v));
     return kn;
 }
 
@@ -59,10 +64,13 @@ struct Work {
     }
 };
 
-// a sub-product: another level where eligible and levels remain, else the plain kernel
+// a sub-product: another level where levels remain and it is eligible under the
+// inner threshold, else the plain kernel
 int Multiply(int levels, const Knobs& kn, Device dev, DType t, bool ta, bool tb, Int m, Int n, Int k, double alpha,
              const void* A, Int lda, const void* B, Int ldb, double beta, void* C, Int ldc, hipStream_t s) {
-    const int used = Gemm(levels, kn, dev, t, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, s);
+    Knobs inner = kn;
+    inner.min = kn.min2;
+    const int used = Gemm(levels, inner, dev, t, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, s);
     if (used == 0) exec::GemmPlain(dev, t, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, s);
     return used;
 }

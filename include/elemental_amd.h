@@ -172,9 +172,11 @@ int elx_gemm_f32(int opA, int opB, int64_t m, int64_t n, int64_t k,
                  const float* B, int64_t ldb,
                  float beta, float* C, int64_t ldc, void* stream);
 /* How many Strassen-Winograd levels the last local GEMM of the calling thread used
- * (0: the plain kernel).  Large f64 / f32 products take one level by default;
- * ELX_GEMM_STRASSEN (0 off, 1, 2 levels) and ELX_GEMM_STRASSEN_MIN (the threshold on
- * min(m, n, k)) are read at every call.  For tests. */
+ * (0: the plain kernel).  Large f64 / f32 products take one level by default, and
+ * two where the half-size products are themselves large enough.  ELX_GEMM_STRASSEN
+ * (0 off, 1, 2 levels), ELX_GEMM_STRASSEN_MIN (the threshold on min(m, n, k)) and
+ * ELX_GEMM_STRASSEN_MIN2 (the threshold on a half-size product's min(m, n, k) for
+ * the second level) are read at every call.  For tests. */
 int elx_gemm_last_levels(void);
 int elx_gemm_f16(int opA, int opB, int64_t m, int64_t n, int64_t k,
                  float alpha, const uint16_t* A, int64_t lda,
